@@ -1,13 +1,19 @@
 #!/usr/bin/env python3
 """Headline benchmark of the hot path (BASELINE.json): eye-frames/s at 320x240.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
 
-A "step" is one pass of the hot path over one synthetic batch that is already resident in HBM.  ONE run
-measures every leg BASELINE.json's metric / north_star name and prints ONE JSON line:
+A "step" is one pass of the hot path over one synthetic batch that is already resident in HBM.  A plain run measures the
+headline leg only: it sets up, runs W warm-up steps, times exactly K steps and prints ONE JSON line with
 
   value / ms_per_step  inference, BASELINE.json configs[1]: frozen BDCN edge extractor -> ESF-Net (baseline_edge,
-                       chz=32) -> loss head + argmax mask, batch 64 per GPU (W warm-up steps, exactly K timed steps);
+                       chz=32) -> loss head + argmax mask, batch 64 per GPU (W warm-up steps, exactly K timed steps).
+
+--dump-outputs DIR writes what the timed path returned in its last timed step as DIR/<name>.npy (see dump_outputs); the
+inputs and weights are seeded, so two builds run with the same arguments can be compared output for output.
+
+--full measures every leg BASELINE.json's metric / north_star name in the same ONE line: besides `value` also
+
   with_fit             the same step followed by evaluate.py's ellipse-fit stage (2 fits per frame, seeds computed on the
                        device, fitted ellipses copied to the host every step): the north-star "edge+seg+fit";
   exact_fp32           the same step with the split-f16 products switched off (every conv on v_mfma_f32_32x32x2_f32);
@@ -15,22 +21,25 @@ measures every leg BASELINE.json's metric / north_star name and prints ONE JSON 
                        step, batch 256 per GPU (BASELINE.json configs[2] shape) with bf16 STORAGE of activations and activation
                        gradients (fp32 accumulation, fp32 master weights: what configs[2..4] name); `train.fp32_storage` is the
                        same step with fp32 storage (the plan the gradient fixtures pin to the reference).  --config
-                       baseline_adain_edge / --chz 64 with --mode train select the configs[3] / configs[4] shapes.
+                       baseline_adain_edge / --chz 64 with --mode train select the configs[3] / configs[4] shapes;
+  latency              one / two frames per call, synchronised after every call (N=1 only).
 
 For N>1 the driver launches one process per GPU (torch.distributed.run, RANK/LOCAL_RANK/WORLD_SIZE in the env);
 `python bench.py --gpus N` without that environment spawns the N rank processes itself (before anything touches the
 GPU in the parent).  Inference shards frames across ranks with no data-path collective (replicas, SURVEY.md 8e);
 training averages gradients with one RCCL all-reduce per step.  Scaling is weak: every rank keeps its own batch.
 
-The JSON line also carries
+The --full line also carries
   roofline      the dominant kernel family of the inference step (split-f16 convolutions: 3 x v_mfma_f32_32x32x16_f16
                 per product): algorithmic conv FLOPs of one step / summed duration of its launches, measured with HIP
                 events on the launch stream inside the timed region, against 2500 / 3 TFLOP/s;
   cpu_baseline  the CPU oracle (oracle/, a port of the reference's PyTorch path) timed on the host cores per BASELINE.md
                 section 3: BDCN forward, ESF forward, ESF forward+backward+Adam and the fit on their own, B=2 and B=8, bounded
                 samples (rank 0 at N=1 only); `parity_sample` compares the GPU path with the oracle on that B=2 sample;
+and every line carries
   ranks         ranks seen, every rank's own frames/s (min / max) and the whole-job value per GPU (= `value` at --gpus 1);
                 training legs add `allreduce_ms_per_step` (HIP events around the RCCL call).
+--mode infer / train / prep run that leg alone, with its roofline (and, for infer / prep, the CPU baseline), --full or not.
 """
 import argparse
 import json
@@ -67,7 +76,7 @@ def parse():
                          "1 (plain f16 operands, fp32 accumulate) next to a bf16-storage plan, which rounds the edge map to bf16 on entry; 3 (the "
                          "22-bit split) next to an fp32-storage plan.  The bf16 leg also reports its rate with 3 (`edge_split3_value`)")
     ap.add_argument("--mode", choices=("all", "infer", "train", "prep"), default="all",
-                    help="all: every leg in one JSON line (default); infer / train: that leg only; "
+                    help="all (default): the headline inference leg, with --full every leg in one JSON line; infer / train: that leg only; "
                          "prep: device-side batch preparation (distance maps + z-score, SURVEY.md 8f N1)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-pipeline", action="store_true", help="inference legs: edge network and ESF-Net of a batch back to back on one stream")
@@ -75,7 +84,7 @@ def parse():
     ap.add_argument("--config", default="baseline_edge", help="configs/<name>.yaml (baseline_adain_edge = BASELINE.json configs[3])")
     ap.add_argument("--chz", type=int, default=32, help="ESF-Net base width (64 = BASELINE.json configs[4]'s wider model)")
     ap.add_argument("--fit", action="store_true", help="--mode infer: the headline step includes the ellipse-fit stage")
-    ap.add_argument("--layers", action="store_true", help="print a per-launch time / TFLOP/s table to stderr")
+    ap.add_argument("--layers", action="store_true", help="print a per-launch time / TFLOP/s table to stderr (--mode infer / train, or --full)")
     ap.add_argument("--force-dist", action="store_true",
                     help="build the RCCL process group even with ONE rank (EGNE_FORCE_DIST=1): the training legs then run the gradient all-reduce, "
                          "the parameter broadcast and the timing all-gather through RCCL and report allreduce_ms_per_step > 0")
@@ -83,6 +92,11 @@ def parse():
     ap.add_argument("--cpu-thread-sweep", action="store_true",
                     help="time the CPU baseline's B=2 edge + seg part at 16 / 32 / 64 / 128 / all logical cores and print the table (one-off: which "
                          "thread count is the fair baseline)")
+    ap.add_argument("--full", action="store_true",
+                    help="--mode all: every leg in one JSON line (the inference roofline region, with_fit, exact_fp32, latency, both training "
+                         "legs, the CPU baseline).  Without it --mode all times the headline inference leg only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path returned in its last step as DIR/<name>.npy (float32 / float64)")
     return ap.parse_args()
 
 
@@ -128,6 +142,32 @@ def _sources_sha16():
         with open(f, "rb") as fh:
             h.update(os.path.basename(f).encode() + b"\0" + fh.read())
     return h.hexdigest()[:16]
+
+
+DUMP_BYTES = 60_000_000     # what --dump-outputs writes in all (the limit is 64 MB)
+
+
+def dump_outputs(d, arrays):
+    """--dump-outputs: ``arrays`` (name -> tensor) as ``d/<name>.npy``, float64 kept, everything else as float32 (class indices
+    included: exact).  Smallest first, an output is written whole while it fits an equal share of what is left of DUMP_BYTES;
+    a larger one as ``<name>_sample.npy``: the flattened array at as many fixed positions as fit that share (sorted, numpy seed 0,
+    the same in every run of the same shapes)."""
+    import numpy as np
+    import torch
+    os.makedirs(d, exist_ok=True)
+    xs = {}
+    for name, t in arrays.items():
+        t = t.detach()
+        xs[name] = (t if t.dtype == torch.float64 else t.float()).cpu().numpy()
+    left = DUMP_BYTES
+    for i, name in enumerate(sorted(xs, key=lambda k: (xs[k].nbytes, k))):
+        x = xs[name]
+        share = left // (len(xs) - i)
+        if x.nbytes > share:
+            idx = np.sort(np.random.default_rng(0).choice(x.size, share // x.itemsize, replace=False))
+            x, name = x.reshape(-1)[idx], name + "_sample"
+        np.save(os.path.join(d, name + ".npy"), x)
+        left -= x.nbytes
 
 
 def _timeit(fn, budget_s, warm=2, lo=5, hi=5):
@@ -269,10 +309,12 @@ def bench_prep(a):
     t0 = time.perf_counter()
     e0.record()
     for _ in range(a.steps):
-        step()
+        out = step()
     e1.record()
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
+    if a.dump_outputs:
+        dump_outputs(a.dump_outputs, dict(zip(("dist_maps", "zscore", "spatial_weights"), out)))
     H, W = lab.shape[1:]
     nbytes = B * H * W * (8 + 3 * 4 + 4 + 4 + 8 + 4)  # label read, 3 maps written, image read + written, label read again + weights written
     ach = nbytes * a.steps / (e0.elapsed_time(e1) * 1e-3) / 1e9
@@ -599,6 +641,8 @@ class Bench:
         B = self.a.batch or 64
         dt, ev, out = self.timed(self.infer_step(B, fit, pipeline), steps, warmup, events)
         assert steps == 0 or self.torch.isfinite(out[3]).all()
+        if steps:        # what a caller of the step receives from the last timed batch (forward's tuple and the argmax mask)
+            self.last_out = dict(zip(("op", "elPred", "latent", "loss", "elOut"), out), mask=self.net.predictions())
         return B, dt, ev
 
     def leg_train(self, steps, warmup, events=True, pipeline=None, storage="fp32", edge_products=None):
@@ -650,6 +694,8 @@ class Bench:
         self.ar_events = []
         dt, ev, out = self.timed(step, steps, warmup, events)
         assert steps == 0 or torch.isfinite(out[3]).all()
+        if steps:        # forward's tuple of the last timed batch (the step's backward / Adam update the model in place)
+            self.last_out = dict(zip(("op", "elPred", "latent", "loss", "elOut"), out))
         ar = [a.elapsed_time(b) for a, b in self.ar_events[-steps:]] if self.ar_events else []
         self.allreduce_ms = round(sum(ar) / len(ar), 4) if ar else 0.0
         self.grad_bytes = int(net._grad_flat.numel() * 4) if getattr(net, "_grad_flat", None) is not None else 0
@@ -701,10 +747,11 @@ def main():
         if rank == 0:
             print(json.dumps({"warmup_only": True, "warmup": a.warmup, "mode": a.mode}), flush=True)
         return
+    lean = a.mode == "all" and not a.full        # a plain run: the headline leg, nothing else
     if a.mode in ("all", "infer"):
         fit_ = a.fit and a.mode == "infer"
         if a.no_pipeline:
-            B, dt, ev = bn.leg_infer(a.steps, a.warmup, fit=fit_)
+            B, dt, ev = bn.leg_infer(a.steps, a.warmup, fit=fit_, events=not lean)
             dt_k = dt
             ranks_inf = bn.rank_report(B, a.steps)
         else:
@@ -713,6 +760,23 @@ def main():
             # stream's kernels (their sum was 1.75x the step), which says nothing about the kernel between them.
             B, dt, _ = bn.leg_infer(a.steps, a.warmup, fit=fit_, events=False)
             ranks_inf = bn.rank_report(B, a.steps)
+        if a.dump_outputs and rank == 0:
+            dump_outputs(a.dump_outputs, bn.last_out)
+        res.update({
+            "value": round(B * a.steps * world / dt, 2), "ms_per_step": round(1e3 * dt / a.steps, 3),
+            "config": {"workload": "BASELINE.json configs[1]: %s.yaml (chz=%d) inference, batch=%d/GPU, fp32, 240x320 synthetic IR "
+                                   "frames, seeded random-init weights" % (a.config, a.chz, B),
+                       "frames_per_gpu_per_step": B, "peak_hbm_gb": round(torch.cuda.max_memory_allocated() / 2 ** 30, 1),
+                       "ellipse_fit_stage": bool(a.fit and a.mode == "infer"), "arithmetic": arith,
+                       "parallelism": "replicas x%d (frames sharded, no collective)" % world,
+                       "pipeline": ("none: edge network and ESF-Net of a batch back to back on one stream" if a.no_pipeline else
+                                    "two stages across batches: the frozen edge network of batch i on one HIP stream while ESF-Net + loss "
+                                    "/ argmax of batch i-1 runs on another; empty when the timed region starts, drained inside it" +
+                                    ("" if lean else " (`roofline` / kernel_time_share: see roofline.measured_in)"))},
+            "ranks": ranks_inf,
+        })
+    if a.mode in ("all", "infer") and not lean:
+        if not a.no_pipeline:
             _, dt_k, ev = bn.leg_infer(a.steps, 1, fit=fit_, pipeline=False)
         fam = bn.families(ev, a.steps, dt_k)
         r_split, r_fp32, sp_t, conv_t = bn.rooflines(fam, a.steps, B, dt_k)
@@ -747,21 +811,10 @@ def main():
             except Exception:
                 continue
         timed_t = sum(v[0] for v in fam.values())
+        res["config"]["peak_hbm_gb"] = round(torch.cuda.max_memory_allocated() / 2 ** 30, 1)
         res.update({
-            "value": round(B * a.steps * world / dt, 2), "ms_per_step": round(1e3 * dt / a.steps, 3),
-            "config": {"workload": "BASELINE.json configs[1]: %s.yaml (chz=%d) inference, batch=%d/GPU, fp32, 240x320 synthetic IR "
-                                   "frames, seeded random-init weights" % (a.config, a.chz, B),
-                       "frames_per_gpu_per_step": B, "peak_hbm_gb": round(torch.cuda.max_memory_allocated() / 2 ** 30, 1),
-                       "ellipse_fit_stage": bool(a.fit and a.mode == "infer"), "arithmetic": arith,
-                       "parallelism": "replicas x%d (frames sharded, no collective)" % world,
-                       "pipeline": ("none: edge network and ESF-Net of a batch back to back on one stream" if a.no_pipeline else
-                                    "two stages across batches: the frozen edge network of batch i on one HIP stream while ESF-Net + loss "
-                                    "/ argmax of batch i-1 runs on another; empty when the timed region starts, drained inside it "
-                                    "(`roofline` / kernel_time_share: see roofline.measured_in)")},
             "roofline": r_split if sp_t >= conv_t else r_fp32, "roofline_secondary": r_fp32 if sp_t >= conv_t else r_split,
             "algorithmic_gflop_per_frame_total": round((r_split["algorithmic_gflop_per_frame"] + r_fp32["algorithmic_gflop_per_frame"]), 2),
-            "kernel_time_share": dict({k.split(":")[0]: 0.0 for k in fam}),
-            "ranks": ranks_inf,
         })
         share = {}
         for k, v in fam.items():
@@ -770,7 +823,7 @@ def main():
             share["untimed (elementwise, reductions, layout, loss, host gaps)"] = 1.0 - timed_t / dt_k
         res["kernel_time_share"] = {k: round(v, 4) for k, v in sorted(share.items())}
 
-    if a.mode == "all":
+    if a.mode == "all" and a.full:
         # ---- edge + seg + fit (north-star target) ----
         B, dt, _ = bn.leg_infer(a.steps, 2, fit=True, events=False)
         res["with_fit"] = {"value": round(B * a.steps * world / dt, 2), "ms_per_step": round(1e3 * dt / a.steps, 3), "steps": a.steps,
@@ -791,22 +844,21 @@ def main():
         _engine.F16X3_ENABLED, _engine.ESF_SPLIT = old
         bn.free_plans()
 
-    if a.mode == "all" and world == 1:
+    if a.mode == "all" and a.full and world == 1:
         # ---- one or two frames per call: the head-mounted-display case (evaluate.py:235-249 feeds one eye at a time) ----
         res["latency_b2_ms"], res["latency"] = bn.leg_latency()
 
-    def train_leg(storage):
+    def train_leg(storage, dump=False):
         steps = a.train_steps if a.mode == "all" else a.steps
         warm = 2 if a.mode == "all" else a.warmup
         bn.free_plans()
         torch.cuda.reset_peak_memory_stats()
-        if a.no_pipeline:
-            B, dt, ev = bn.leg_train(steps, warm, storage=storage)
-            dt_k = dt
-            ranks = bn.rank_report(B, steps)
-        else:       # value from the pipelined loop, kernel durations from a second region with the stages back to back (as for inference)
-            B, dt, _ = bn.leg_train(steps, warm, events=False, storage=storage)
-            ranks = bn.rank_report(B, steps)
+        B, dt, ev = bn.leg_train(steps, warm, events=a.no_pipeline, storage=storage)
+        ranks = bn.rank_report(B, steps)
+        if dump and a.dump_outputs and rank == 0:
+            dump_outputs(a.dump_outputs, bn.last_out)
+        dt_k = dt
+        if not a.no_pipeline:       # value from the pipelined loop, kernel durations from a second region with the stages back to back (as for inference)
             _, dt_k, ev = bn.leg_train(steps, 1, pipeline=False, storage=storage)
         fam = bn.families(ev, steps, dt_k)
         rsp, r32, sp_t, conv_t = bn.rooflines(fam, steps, B, dt_k, products=1 if (storage == "bf16" and bn.edge_products == 1) else 3)
@@ -870,9 +922,9 @@ def main():
         bn.free_plans()
         return tr, rdom, rsec
 
-    if a.mode in ("all", "train"):
+    if a.mode == "train" or (a.mode == "all" and a.full):
         first = "bf16" if a.train_storage in ("bf16", "both") else "fp32"
-        tr, rdom, rsec = train_leg(first)
+        tr, rdom, rsec = train_leg(first, dump=a.mode == "train")
         if a.train_storage == "both":
             tr["fp32_storage"], _, _ = train_leg("fp32")        # the parity anchor (the gradient fixtures pin THIS plan to the reference's fp32 gradients)
             tr["fp32_storage"].pop("roofline_secondary", None)
@@ -893,7 +945,7 @@ def main():
             res["train"] = tr
 
     if rank == 0:
-        if world == 1 and not a.no_cpu_baseline and a.mode != "train":
+        if world == 1 and not a.no_cpu_baseline and a.mode != "train" and not lean:
             res["cpu_baseline"] = cpu_baseline(bn.setting, bn.bd_sd, bn.net_sd, budget_s=a.cpu_budget, parity=bn.parity_sample, threads=a.cpu_threads)
             if a.cpu_thread_sweep:
                 res["cpu_thread_sweep"] = cpu_thread_sweep(bn.setting, bn.bd_sd, bn.net_sd)

@@ -8,7 +8,7 @@ out=$R/gpurun_out/$tag
 mkdir -p $out
 cd /tmp && export TMPDIR=/tmp
 if [ "$only" = all ] || [ "$only" = bench ]; then
-python3 $R/bench.py --steps 20 --warmup 5 > $out/bench.json 2> $out/bench.err
+python3 $R/bench.py --full --steps 20 --warmup 5 > $out/bench.json 2> $out/bench.err
 python3 $R/bench.py --mode train --steps 4 --warmup 2 --train-batch 256 --config baseline_adain_edge --train-storage bf16 > $out/bench_train_adain_bf16.json 2>/dev/null
 python3 $R/bench.py --mode train --steps 4 --warmup 2 --train-batch 256 --chz 64 --train-storage bf16 > $out/bench_train_chz64_bf16.json 2>/dev/null
 python3 $R/bench.py --mode infer --steps 10 --warmup 3 --no-cpu-baseline --no-pipeline --layers > $out/bench_layers.json 2> $out/per_layer_table.txt

@@ -430,6 +430,31 @@ def test_entry_args_and_checkpoint_format():
     assert len(s) == 9 and tuple(s[0].shape) == (1, 240, 320) and s[7].dtype == torch.bool and tuple(s[8].shape) == (3,)
 
 
+def test_bench_dump_outputs_float_arrays_and_a_fixed_sample(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: float32 files (float64 kept, class indices exact), within DUMP_BYTES in all; outputs too large for
+    their share written as the same sample of their positions in every run, so two runs (two builds) compare file for file."""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("egne_bench", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    monkeypatch.setattr(bench, "DUMP_BYTES", 40000)
+    arrays = {"op": torch.arange(8000, dtype=torch.float32).view(-1, 8), "edge": torch.arange(6000, dtype=torch.float32) + 0.5,
+              "mask": torch.tensor([[0, 2], [1, 2]]), "fit": torch.tensor([0.1, 1e-300], dtype=torch.float64),
+              "latent": torch.ones(2, 3, dtype=torch.bfloat16)}
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), arrays)
+    assert sorted(os.listdir(tmp_path / "a")) == ["edge_sample.npy", "fit.npy", "latent.npy", "mask.npy", "op_sample.npy"]
+    assert sum(os.path.getsize(tmp_path / "a" / f) - 128 for f in os.listdir(tmp_path / "a")) <= 40000       # (npy header: 128 bytes)
+    for f in os.listdir(tmp_path / "a"):
+        x, y = np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f)
+        assert x.dtype in (np.float32, np.float64) and np.array_equal(x, y), f
+    for f, n in (("op_sample", 8000), ("edge_sample", 6000)):
+        s = np.load(tmp_path / "a" / (f + ".npy"))
+        assert 4900 <= s.size < 5000 and np.all(np.diff(s) > 0) and s[-1] < n + 0.5      # distinct positions, in order
+    assert np.array_equal(np.load(tmp_path / "a" / "mask.npy"), np.array([[0, 2], [1, 2]], np.float32))
+    assert np.load(tmp_path / "a" / "fit.npy").dtype == np.float64 and np.load(tmp_path / "a" / "latent.npy").shape == (2, 3)
+
+
 def test_bench_refuses_a_world_that_does_not_match_gpus():
     """bench.py --gpus N must either run N ranks or fail loudly (round 1 silently ran one rank)."""
     env = dict(os.environ, WORLD_SIZE="1", RANK="0", LOCAL_RANK="0")
