@@ -912,7 +912,10 @@ class Plan:
             if int(self.ovf.item()) == 0:
                 return False
         else:
-            if not getattr(self, "_ovf_recorded", False) or not self.ovf_event.query() or int(self.ovf_host[0]) == 0:
+            # (an event cannot be queried while the stream is being captured: GraphedFrames capturing a plan whose mirror copy has
+            # been queued before -- the callers of a replay ask with ``wait`` where they synchronise)
+            if (not getattr(self, "_ovf_recorded", False) or torch.cuda.is_current_stream_capturing() or not self.ovf_event.query()
+                    or int(self.ovf_host[0]) == 0):
                 return False
         self._ovf_reset()
         return True

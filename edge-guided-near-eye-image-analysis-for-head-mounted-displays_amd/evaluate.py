@@ -7,6 +7,7 @@ videos/example1.avi) are decoded with PIL, results go to <video>_ellipses.npy in
 
     python evaluate.py --path2data videos [--max_frames 20]
     python evaluate.py --synthetic 4
+    python evaluate.py --path2data videos --low_latency 1 --device_io 1     (frame prep and overlay rendering on the device)
 """
 import argparse
 import glob
@@ -36,6 +37,8 @@ def parse_args(argv=None):
     p.add_argument('--max_frames', type=int, default=0)
     p.add_argument('--synthetic', type=int, default=0)
     p.add_argument('--low_latency', type=int, default=0)          # 1: the two eyes of a frame per call, results before the next frame
+    p.add_argument('--eye_width', type=int, default=320)          # columns per eye of a video frame (two eyes side by side; evaluate.py:235-249: 320)
+    p.add_argument('--device_io', type=int, default=0, choices=(0, 1))   # 1: frame prep and overlay rendering on the device (csrc/evalio.hip)
     a = p.parse_args(argv)
     a.prec = torch.float32
     return a
@@ -132,11 +135,12 @@ def _overflowed(net):
     return bool(net.overflowed()) if hasattr(net, "overflowed") else False
 
 
-def _seg_and_fit(frames, model, wfit=None):
+def _seg_and_fit(frames, model, wfit=None, then=None):
     """Second stage of a batch (evaluate.py:117-166): ESF-Net on the frames and their edge maps, argmax mask, both ellipses
     fitted on the device.  Returns a callable of the edge maps (egne_amd.pipeline.TwoStagePipeline runs it on its second stream).
     ``wfit`` (egne_amd.pipeline.WindowedFit): the searches go to its stream and are released in the next batch's launch window; the
-    third result is then a handle (``_to_host`` waits for it)."""
+    third result is then a handle (``_to_host`` waits for it); ``then(edge, mask, fit)`` is queued on the searches' stream right behind
+    them (the device-side rendering of --device_io 1)."""
     dev = frames.device
     N, _, H, W = frames.shape
 
@@ -149,7 +153,8 @@ def _seg_and_fit(frames, model, wfit=None):
             out = model(frames, edge, labels.long(), z(N, 2), z(N, 2, 5), z(N, H, W), z(N, 3, H, W), z(N, 4),
                         torch.zeros(N, dtype=torch.long, device=dev), 0)
             if wfit is not None:
-                return edge[:, 0].clone(), model.predictions().clone(), wfit.submit(model.predictions(), out[1])
+                e, m = edge[:, 0].clone(), model.predictions().clone()
+                return e, m, wfit.submit(model.predictions(), out[1], then=None if then is None else (lambda fit: then(e, m, fit)))
             fit = fit_ellipses_from_pred(model.predictions(), out[1])     # [N,2,5] on the device: (iris, pupil)
             return edge[:, 0].clone(), model.predictions().clone(), fit
     return run
@@ -166,6 +171,55 @@ def graphed_runner(warmup_frames, model, edge_model):
     def stage(x):
         return _seg_and_fit(x, model)(calc_edge(ns, x, edge_model, x.device))
     return GraphedFrames(stage, warmup_frames)
+
+
+def graphed_runner_io(warmup_u8, model, edge_model, op_shape=(240, 320), eyes=2, eye_width=320):
+    """graphed_runner with the device front and back end INSIDE the captured graph: uint8 frames [N,Hs,Ws] in, (overlay, edge frame,
+    ellipses at source geometry) out -- prep, edge, seg, fit and rendering are one replay.  Capture allows it: shapes are fixed, the
+    tap tables are uploaded by the eager warm-up runs, nothing in the two stages synchronises."""
+    from egne_amd.pipeline import GraphedFrames
+    from egne_amd.utils import calc_edge
+    ns = argparse.Namespace(prec=torch.float32, edge_thres=0)
+
+    def stage(fu):
+        x, ss = preprocess_frames_device(fu, op_shape, eyes, eye_width)
+        edge, seg, fit = _seg_and_fit(x, model)(calc_edge(ns, x, edge_model, x.device))
+        return render_frames_device(fu, edge, seg, fit, ss, eyes, eye_width)
+    return GraphedFrames(stage, warmup_u8)
+
+
+def evaluate_frames_device_io(frames_u8, model, edge_model, op_shape=(240, 320), eyes=2, eye_width=320):
+    """evaluate_ellseg_on_image from uint8 device frames to rendered device frames (eager; the redo path of --device_io 1): the same
+    re-calibration retries, nothing crosses to the host but the plans' overflow words."""
+    from egne_amd.utils import calc_edge
+    ns = argparse.Namespace(prec=torch.float32, edge_thres=0)
+    x, ss = preprocess_frames_device(frames_u8, op_shape, eyes, eye_width)
+    for attempt in (0, 1, 2):
+        with torch.no_grad():
+            edge = calc_edge(ns, x, edge_model, x.device)
+        if _overflowed(edge_model):
+            continue
+        e, m, fit = _seg_and_fit(x, model)(edge)
+        if not _overflowed(model):
+            return render_frames_device(frames_u8, e, m, fit, ss, eyes, eye_width)
+    raise RuntimeError("non-finite activations after re-calibration: the input frames themselves are not finite")
+
+
+def _upload_u8(frames, device):
+    """The only host -> device copy of --device_io 1: the decoded frames as they are, uint8 [N,Hs,Ws]."""
+    return torch.from_numpy(np.ascontiguousarray(frames)).to(device)
+
+
+def _download(t):
+    """The only device -> host copies of --device_io 1 go through here: two uint8 BGR frames and 20 doubles per eye."""
+    return t.cpu().numpy()
+
+
+class _Batch(list):
+    """Frames of a batch whose results are still on the device; with --device_io 1 also their uint8 device copy (kept for the
+    rendering and for a redo) and the rendered tensors once the fit's stream has queued them."""
+    fu = None
+    rendered = None
 
 
 def _to_host(res):
@@ -221,6 +275,129 @@ def plot_segmap_ellpreds(image, seg_map, pupil_ellipse, iris_ellipse):
     _draw_ellipse(out, iris_ellipse, np.array([255, 0, 0], np.uint8))
     _draw_ellipse(out, pupil_ellipse, np.array([0, 0, 255], np.uint8))
     return out
+
+
+_LANCZOS_TABLES, _DEVICE_TABLES = {}, {}
+
+
+def lanczos4_table(n1, n2):
+    """Tap tables of resize_lanczos4 for one axis resized from ``n1`` to ``n2`` samples: (indices int32 [n2,8], clamped to the border,
+    weights float64 [n2,8], normalised) -- the same expressions, hence the same bits, as resize_lanczos4 evaluates.  Cached."""
+    key = (int(n1), int(n2))
+    if key not in _LANCZOS_TABLES:
+        n1, n2 = key
+        pos = (np.arange(n2) + 0.5) * (n1 / n2) - 0.5
+        base = np.floor(pos).astype(np.int64)
+        frac = pos - base
+        taps = np.arange(-3, 5)
+        x = frac[:, None] - taps[None, :]
+        with np.errstate(invalid="ignore", divide="ignore"):
+            wts = np.where(np.abs(x) < 1e-12, 1.0, np.sin(np.pi * x) * np.sin(np.pi * x / 4) / (np.pi * np.pi * x * x / 4))
+        wts = np.where(np.abs(x) < 4, wts, 0.0)
+        wts /= wts.sum(1, keepdims=True)
+        idx = np.clip(base[:, None] + taps[None, :], 0, n1 - 1)
+        _LANCZOS_TABLES[key] = (np.ascontiguousarray(idx.astype(np.int32)), np.ascontiguousarray(wts))
+    return _LANCZOS_TABLES[key]
+
+
+def _device_table(key, device, make):
+    """Small constant tables of the device front / back end, uploaded once per device (not inside a graph capture: the eager
+    warm-up runs of GraphedFrames come first)."""
+    k = (key, str(device))
+    if k not in _DEVICE_TABLES:
+        _DEVICE_TABLES[k] = tuple(torch.from_numpy(a).to(device) for a in make())
+    return _DEVICE_TABLES[k]
+
+
+def _outline_table():
+    t = np.linspace(0, 2 * np.pi, 720, endpoint=False)      # _draw_ellipse's samples
+    return (np.stack([np.cos(t), np.sin(t)]),)
+
+
+def prep_geometry(src_hw, op_shape):
+    """The shape arithmetic of preprocess_frame for an eye of ``src_hw`` = (rows, columns): returns (resized rows, resized columns,
+    scale_shift)."""
+    He, We = int(src_hw[0]), int(src_hw[1])
+    Ho, Wo = int(op_shape[0]), int(op_shape[1])
+    Hr, Wr, scale_shift = He, We, (1, 0)
+    if Wo != We:
+        sc = Wo / We
+        Wr, Hr = int(We * sc), int(He * sc)
+        scale_shift = (sc, 0)
+    if Ho > Hr:
+        scale_shift = (scale_shift[0], Ho - Hr)
+    elif Ho < Hr:
+        scale_shift = (scale_shift[0], -(Hr - Ho))
+    return Hr, Wr, scale_shift
+
+
+def _check_frames(frames_u8, eyes, eye_width):
+    from egne_amd.engine import require_cuda
+    require_cuda(frames_u8, "frames_u8")
+    if frames_u8.dtype != torch.uint8 or frames_u8.dim() != 3:
+        raise ValueError("frames_u8 must be a uint8 [N,H,W] tensor")
+    if eyes < 1 or eye_width < 1 or eyes * eye_width > frames_u8.shape[2]:
+        raise ValueError("%d eyes of %d columns do not fit frames of %d columns" % (eyes, eye_width, frames_u8.shape[2]))
+    return frames_u8.contiguous()
+
+
+def preprocess_frames_device(frames_u8, op_shape, eyes=2, eye_width=320, return_u8=False):
+    """preprocess_frame(grey, op_shape, align_width=True) of every eye of a batch of video frames, on the device (egne_eval_prep):
+    ``frames_u8`` uint8 [N,Hs,Ws] on the GPU, eye i of a frame = columns [i*eye_width, (i+1)*eye_width).  Returns (x float32
+    [N*eyes,1,Ho,Wo], frame-major then eye -- bit-identical to the stacked host results --, scale_shift); with ``return_u8`` also the
+    uint8 image [N*eyes,Ho,Wo] after resize / pad / crop, before the z-score.  Queues on the current stream, no synchronisation."""
+    from egne_amd import _lib
+    f = _check_frames(frames_u8, eyes, eye_width)
+    N, Hs, Ws = f.shape
+    Ho, Wo = int(op_shape[0]), int(op_shape[1])
+    Hr, Wr, scale_shift = prep_geometry((Hs, eye_width), (Ho, Wo))
+    if Wr != Wo or Hr < 1:
+        raise ValueError("eyes of %dx%d resize to %dx%d, not to the target width %d" % (Hs, eye_width, Hr, Wr, Wo))
+    L = _lib.lib()
+    rows = _device_table(("lanczos", Hs, Hr), f.device, lambda: lanczos4_table(Hs, Hr)) if Hr != Hs else (None, None)
+    cols = _device_table(("lanczos", eye_width, Wr), f.device, lambda: lanczos4_table(eye_width, Wr)) if Wr != eye_width else (None, None)
+    resize = int(rows[0] is not None or cols[0] is not None)
+    x = torch.empty((N * eyes, 1, Ho, Wo), dtype=torch.float32, device=f.device)
+    u8 = torch.empty((N * eyes, Ho, Wo), dtype=torch.uint8, device=f.device) if return_u8 else None
+    ws = torch.empty(int(L.egne_eval_prep_workspace_bytes(N, eyes, Hr, Wr, resize)), dtype=torch.uint8, device=f.device)
+    ptr = lambda t: None if t is None else t.data_ptr()       # noqa: E731
+    _lib.check(L.egne_eval_prep(f.data_ptr(), N, Hs, Ws, eyes, eye_width, Hr, Wr, ptr(rows[0]), ptr(rows[1]), ptr(cols[0]), ptr(cols[1]),
+                                Ho, Wo, x.data_ptr(), ptr(u8), ws.data_ptr(), _lib.stream_ptr()), "eval_prep")
+    return (x, scale_shift, u8) if return_u8 else (x, scale_shift)
+
+
+def render_frames_device(frames_u8, edge, seg, fit, scale_shift, eyes=2, eye_width=320):
+    """The back end of draw() on the device (egne_eval_render): ``frames_u8`` uint8 [N,Hs,Ws] (the frames the maps were computed
+    from), ``edge`` float32 [N*eyes,Ho,Wo], ``seg`` int64 [N*eyes,Ho,Wo] (model.predictions()), ``fit`` float64 [N*eyes,2,5] (iris,
+    pupil) as fit_ellipses_from_pred leaves it, ``scale_shift`` from preprocess_frames_device.  Returns device tensors (overlay uint8
+    [N,Hs,Ws,3] BGR, edge frame uint8 [N,Hs,Ws,3], ellipses float64 [N*eyes,2,5] at source geometry) -- byte for byte what
+    rescale_to_original + plot_segmap_ellpreds + the edge-frame expression give per eye.  No synchronisation."""
+    from egne_amd import _lib
+    from egne_amd.engine import require_cuda
+    f = _check_frames(frames_u8, eyes, eye_width)
+    N, Hs, Ws = f.shape
+    E = N * eyes
+    for t, what in ((edge, "edge"), (seg, "seg"), (fit, "fit")):
+        require_cuda(t, what)
+    if seg.dtype != torch.int64 or seg.dim() != 3 or seg.shape[0] != E:
+        raise ValueError("seg must be an int64 [%d,Ho,Wo] tensor" % E)
+    if edge.dtype != torch.float32 or tuple(edge.shape) != tuple(seg.shape):
+        raise ValueError("edge must be a float32 tensor of the class maps' shape %s" % (tuple(seg.shape),))
+    if fit.dtype != torch.float64 or tuple(fit.shape) != (E, 2, 5):
+        raise ValueError("fit must be a float64 [%d,2,5] tensor" % E)
+    Ho, Wo = int(seg.shape[1]), int(seg.shape[2])
+    scale, shift = scale_shift
+    if int(shift) != shift or shift >= Ho or not scale > 0:
+        raise ValueError("scale_shift %r does not belong to maps of %d rows" % (scale_shift, Ho))
+    cs, = _device_table("outline", f.device, _outline_table)
+    overlay = torch.empty((N, Hs, Ws, 3), dtype=torch.uint8, device=f.device)
+    edge_frame = torch.empty_like(overlay)
+    ell = torch.empty((E, 2, 5), dtype=torch.float64, device=f.device)
+    edge, seg, fit = edge.contiguous(), seg.contiguous(), fit.contiguous()
+    _lib.check(_lib.lib().egne_eval_render(f.data_ptr(), N, Hs, Ws, eyes, eye_width, seg.data_ptr(), edge.data_ptr(), fit.data_ptr(), Ho, Wo,
+                                           1 / scale, int(shift), cs.data_ptr(), overlay.data_ptr(), edge_frame.data_ptr(), ell.data_ptr(),
+                                           _lib.stream_ptr()), "eval_render")
+    return overlay, edge_frame, ell
 
 
 class MJPEGWriter:
@@ -300,12 +477,16 @@ def evaluate_ellseg_per_video(path_vid, args, model, edge_model, device):
     ready = []
 
     redo = [False]
+    io = bool(getattr(args, 'device_io', 0))        # frame prep and rendering on the device: uint8 frames up, uint8 frames + ellipses down
+    ew = int(getattr(args, 'eye_width', 320))
     live = bool(getattr(args, 'low_latency', 0))    # head-mounted-display use: a frame's ellipses before the next frame arrives
     runner = [None]
 
     def flush():
         if not pending:
             return
+        if io:
+            return flush_io()
         eyes = [e for fr in pending for e in fr[2]]
         x = torch.stack([e[0] for e in eyes]).to(device)
         if live:
@@ -334,12 +515,67 @@ def evaluate_ellseg_per_video(path_vid, args, model, edge_model, device):
         while len(ready) > 1:
             draw(*ready.pop(0))
 
+    def flush_io():
+        batch = _Batch(pending)
+        pending.clear()
+        batch.fu = _upload_u8(np.stack([fr for _, fr, _ in batch]), device)
+        if live:
+            # prep and rendering are part of the replay: one graph from the uint8 frame to the two uint8 frames
+            if runner[0] is None or tuple(runner[0].x.shape) != tuple(batch.fu.shape):
+                runner[0] = graphed_runner_io(batch.fu, model, edge_model, (240, 320), 2, ew)
+            res = runner[0](batch.fu)
+            if _overflowed(model) | _overflowed(edge_model):
+                runner[0] = graphed_runner_io(batch.fu, model, edge_model, (240, 320), 2, ew)
+                res = runner[0](batch.fu)
+                if _overflowed(model) | _overflowed(edge_model):
+                    raise RuntimeError("non-finite activations after re-calibration: the input frames themselves are not finite")
+            batch.rendered = tuple(res)
+            done = torch.cuda.Event()
+            done.record()
+            draw_io(batch, (None, done))
+            return
+        x, ss = preprocess_frames_device(batch.fu, (240, 320), 2, ew)
+
+        def then(e, m, fit):                  # on the searches' stream, right behind them (WindowedFit.submit)
+            batch.rendered = render_frames_device(batch.fu, e, m, fit, ss, 2, ew)
+        queued.append(batch)
+        r = pipe.submit(x, _seg_and_fit(x, model, wfit, then))
+        if r is not None:
+            ready.append((queued.pop(0), r))
+        while len(ready) > 1:
+            draw_io(*ready.pop(0))
+
+    def draw_io(batch, r):
+        nonlocal vid_out, edge_out
+        res, done = r
+        done.synchronize()
+        if res is not None:
+            res[2].synchronize()        # WindowedFit.Handle: queues the searches (and the rendering behind them) if their window never opened
+        if redo[0] or _overflowed(model) | _overflowed(edge_model):
+            # as draw(): this batch and the one queued behind it again, from the retained uint8 device frames, rendered again
+            redo[0] = not redo[0]
+            torch.cuda.synchronize()
+            batch.rendered = evaluate_frames_device_io(batch.fu, model, edge_model, (240, 320), 2, ew)
+        overlay, edge_frame, ell = (_download(t) for t in batch.rendered)
+        for n, (j, fr, _) in enumerate(batch):
+            for i in range(2):
+                q, p = ell[2 * n + i, 0].copy(), ell[2 * n + i, 1].copy()
+                out[j] = (q, p)
+                out[(j, i)] = (q, p)
+            _put_frame_number(overlay[n], j)
+            if vid_out is None:
+                Hh, Ww = fr.shape[:2]
+                vid_out = MJPEGWriter(stem + '_result_' + args.method + '.avi', 30, (Ww, Hh))
+                edge_out = MJPEGWriter(stem + '_edge_' + args.method + '.avi', 30, (Ww, Hh))
+            vid_out.write(overlay[n])
+            edge_out.write(edge_frame[n])
+
     def drain():
         r = pipe.flush()
         if r is not None and queued:
             ready.append((queued.pop(0), r))
         while ready:
-            draw(*ready.pop(0))
+            (draw_io if io else draw)(*ready.pop(0))
 
     def draw(frames_of_batch, r):
         nonlocal vid_out, edge_out
@@ -361,8 +597,8 @@ def evaluate_ellseg_per_video(path_vid, args, model, edge_model, device):
                 sm, p, q, em = rescale_to_original(seg[k], pup[k], iri[k], ss, grey.shape, edge_map=em)
                 out[j] = (q, p)                                                      # evaluate.py:269 (the second eye overwrites the first)
                 out[(j, i)] = (q, p)
-                overlay[:, 320 * i: 320 * (i + 1)] = plot_segmap_ellpreds(grey, sm, p, q)
-                edge_frame[:, 320 * i: 320 * (i + 1)] = np.clip(em, 0, 255).astype(np.uint8)[..., None]
+                overlay[:, ew * i: ew * (i + 1)] = plot_segmap_ellpreds(grey, sm, p, q)
+                edge_frame[:, ew * i: ew * (i + 1)] = np.clip(em, 0, 255).astype(np.uint8)[..., None]
                 k += 1
             _put_frame_number(overlay, j)
             if vid_out is None:
@@ -375,13 +611,18 @@ def evaluate_ellseg_per_video(path_vid, args, model, edge_model, device):
     for j, fr in enumerate(mjpeg_frames(path_vid)):
         if args.max_frames and j >= args.max_frames:
             break
-        frame_bgr = np.stack([fr] * 3, axis=2)
-        eyes = []
-        for i in range(2):
-            grey = fr[:, 320 * i: 320 * (i + 1)]
-            t, ss = preprocess_frame(grey, (240, 320), args.align_width)
-            eyes.append((t, ss, grey))
-        pending.append((j, frame_bgr, eyes))
+        if io:
+            if not args.align_width:
+                sys.exit('Height alignment not implemented! Exiting ...')
+            pending.append((j, fr, None))       # the decoded frame as it is: prep and rendering run on the device
+        else:
+            frame_bgr = np.stack([fr] * 3, axis=2)
+            eyes = []
+            for i in range(2):
+                grey = fr[:, ew * i: ew * (i + 1)]
+                t, ss = preprocess_frame(grey, (240, 320), args.align_width)
+                eyes.append((t, ss, grey))
+            pending.append((j, frame_bgr, eyes))
         if len(pending) >= (1 if live else 16):
             flush()
     flush()

@@ -678,6 +678,35 @@ int egne_spatial_weights(const int64_t* label, int B, int H, int W, float* out, 
 int egne_augment(const uint8_t* img, const int64_t* label, const int32_t* choice, const double* param, const uint8_t* lut,
                  const double* noise, uint8_t* out_img, int64_t* out_label, int B, int H, int W, void* stream);
 
+/* Device-side front and back end of evaluate.py (--device_io 1; csrc/evalio.hip), pinned bit for bit against the host functions there.
+ * egne_eval_prep: preprocess_frame(grey, (Ho, Wo), align_width=True) for every eye of a batch of video frames.  src uint8 [N,Hs,Ws];
+ *   eye e of frame n is columns [e*We, (e+1)*We) (eyes*We <= Ws); out float32 [N*eyes,1,Ho,Wo], frame-major then eye.
+ *   (Hr, Wr) = shape of an eye after the Lanczos resize (int(Hs*sc), int(We*sc), sc = Wo/We; Wr must equal Wo; Hr = Hs, Wr = We
+ *   when nothing is resized).  row_idx / row_w [Hr][8] and col_idx / col_w [Wr][8]: the 8 source indices (already clamped to the
+ *   border) and normalised float64 weights of every output row / column, exactly as evaluate.resize_lanczos4 builds them
+ *   (evaluate.lanczos4_table); a NULL pair skips that pass (its source and resized extent must then agree).  Rows first (sequential
+ *   float64 sum), then columns (pairwise float64 sum) with no rounding in between, clip(rint(.), 0, 255).  Rows: zero-padded
+ *   (Ho-Hr)/2 above when Hr < Ho, centre-cropped from (Hr-Ho)/2 when Hr > Ho.  z-score from exact 64-bit integer sums S, Q over the
+ *   padded image of n = Ho*Wo pixels: mean = S/n, std = sqrt(n*Q - S*S)/n in float64, out = float((x - mean) / std); a constant
+ *   image gives NaN as on the host.  u8_out (optional, may be NULL) uint8 [N*eyes,Ho,Wo]: the resized, padded image before the
+ *   z-score.  ws: egne_eval_prep_workspace_bytes(N, eyes, Hr, Wr, resize) bytes, resize = 1 when either tap table is given.
+ * egne_eval_render: the two uint8 BGR frames of evaluate.py's draw() and the ellipses at source geometry.  src as above; seg int64
+ *   [N*eyes,Ho,Wo] class maps, edge float32 [N*eyes,Ho,Wo], fit float64 [N*eyes,2,5] (iris, pupil) x (cx,cy,a,b,theta) at network
+ *   geometry; inv_scale = 1 / scale and shift = rows added (+) or removed (-) by the front end (its scale_shift); cos_sin float64
+ *   [2][720] = cos(t), sin(t) of t = linspace(0, 2 pi, 720, endpoint=False).  ell_out float64 [N*eyes,2,5]: rescale_to_original
+ *   (e[1] -= shift // 2, e[:4] *= inv_scale).  overlay / edge_frame uint8 [N,Hs,Ws,3]: class and edge maps un-padded / zero
+ *   re-padded and nearest-resized (floor(dst * n1 / n2), clamped) to (Hs, We) per eye; overlay = grey, class 1 (120,183,53), class 2
+ *   (36,231,253), iris outline (255,0,0), pupil outline (0,0,255), outlines as evaluate._draw_ellipse (skipped when all -1 or
+ *   non-finite, truncated centre / axes, 720 samples, rint, clipped to the eye); edge_frame = clip(255 - 255*edge, 0, 255) truncated,
+ *   formed in float32 at network geometry (re-padded rows are 0); columns beyond eyes*We are copied from src in both frames. */
+int64_t egne_eval_prep_workspace_bytes(int N, int eyes, int Hr, int Wr, int resize);
+int egne_eval_prep(const uint8_t* src, int N, int Hs, int Ws, int eyes, int We, int Hr, int Wr, const int32_t* row_idx,
+                   const double* row_w, const int32_t* col_idx, const double* col_w, int Ho, int Wo, float* out,
+                   uint8_t* u8_out, void* ws, void* stream);
+int egne_eval_render(const uint8_t* src, int N, int Hs, int Ws, int eyes, int We, const int64_t* seg, const float* edge,
+                     const double* fit, int Ho, int Wo, double inv_scale, int shift, const double* cos_sin,
+                     uint8_t* overlay, uint8_t* edge_frame, double* ell_out, void* stream);
+
 /*
  * ---- bf16 activation storage (training plans; BASELINE.json configs[2..4], reference loop train.py:262-287, --prec args.py:17-28) ----
  * Twins of the entry points above for plans that keep activations and activation gradients in HBM as bf16 (NHWC, strides and
