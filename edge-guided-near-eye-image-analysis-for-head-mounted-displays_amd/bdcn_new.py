@@ -127,8 +127,18 @@ class BDCN(nn.Module):
                     p.normal_(0, 0.01)
 
     # ------------------------------------------------------------------------------------------
-    def _build(self, B, H, W, dev, only_fuse, edge_thres, f16_storage=None):
+    def _build(self, B, H, W, dev, only_fuse, edge_thres, f16_storage=None, split3=False):
         if f16_storage is None:
+            # calibrated three-product inference plan: conv3_1 .. conv5_3, pool3 / pool4 in channel-order split-pair storage (egne_conv_desc.out_split = 3),
+            # written once by their producers and copied by every reader; fp32 tensors where a chosen kernel does not know the storage (batches too small
+            # for the deep trunk kernel)
+            # (the deep trunk kernel takes a layer from 32 768 output pixels on; stages 4 and 5 run at 1/8 of the frame: smaller batches are not tried)
+            h8, w8 = (maxpool_out(maxpool_out(maxpool_out(n, 2), 2), 2) for n in (H, W))
+            if engine.PRESPLIT_TRUNK and engine.CALIBRATE and getattr(self, "_plan_products", 0) != 1 and B * h8 * w8 >= 256 * 128:
+                try:
+                    return self._build(B, H, W, dev, only_fuse, edge_thres, 0, True)
+                except engine.NeedsFp32Storage:
+                    pass
             # plain-f16 plans: conv1_1 / conv1_2 / pool1 as F16 tensors (egne_conv_desc.out_split = 2) -- their consumers round every operand
             # to exactly the stored value anyway, so nothing changes but the bytes; fp32 tensors where a chosen kernel does not know the storage
             # (level 2: also the outputs of conv3_1 .. conv5_3 and pool3 / pool4 -- deep trunk kernel, streamed-weights 3x3 and pooling read them)
@@ -141,6 +151,7 @@ class BDCN(nn.Module):
             return self._build(B, H, W, dev, only_fuse, edge_thres, 0)
         pl = Plan(dev)
         pl.f16_storage = int(f16_storage)
+        pl.split3_trunk = bool(split3)
         # BDCN.f16_products = 1: plain f16 operands (one MFMA per product instead of the split's three) in the kernels that know
         # egne_conv_desc.f16_products -- the frozen edge network next to a training plan with bf16 activation storage, which rounds
         # the edge map to bf16 on entry (train.py / bench.py set it for --prec 16 only; inference and fp32 storage keep the split)
@@ -275,6 +286,7 @@ class BDCN(nn.Module):
                     ob = (pl.buf16 if c16 is not None else pl.buf)(B, ho, wo, cur.Cp)
                     dst = Piece(ob, 0, cur.C)
                     dst.f16s = c16
+                    dst.split3 = cur.split3
                     pl.maxpool2(cur, dst, B, hh, ww, s, "vgg.pool")
                 cur, hh, ww, pooled = dst, ho, wo, None
                 continue
@@ -288,6 +300,8 @@ class BDCN(nn.Module):
             dst = Piece(ob, 0, cout)
             if h16:
                 dst.f16s = engine.SplitScale()
+            if split3 and name[4] in "345":
+                dst.split3 = engine.SplitScale()
             nxt = _VGG[idx + 1] if idx + 1 < len(_VGG) else None
             pq = None
             if nxt is not None and nxt[0] == "P" and nxt[1] == 2:         # vgg16_c.py:70: pooling right behind this convolution

@@ -123,6 +123,13 @@ inline int fail(int code, const char* fmt, ...) {
   return code;
 }
 
+// Entry points that know neither split-pair nor f16 storage (egne_seg.presplit, egne_conv_desc.out_split) reject a descriptor that asks for one.
+inline bool fp32_storage(const egne_conv_desc& d) {
+  for (int i = 0; i < d.nseg && i < EGNE_MAXSEG; ++i)
+    if (d.seg[i].presplit != 0) return false;
+  return d.out_split == 0;
+}
+
 inline int check_launch(const char* what) {
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return fail(EGNE_ERR_LAUNCH, "%s: %s", what, hipGetErrorString(e));

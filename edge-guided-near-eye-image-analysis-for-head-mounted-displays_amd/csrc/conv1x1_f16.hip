@@ -361,6 +361,7 @@ extern "C" int egne_conv1x1_f16x3_fwd(const egne_conv_desc* dp, const void* fhi,
                                       void* stream) {
   EGNE_REQUIRE(dp && fhi && flo, "conv1x1_f16: null pointer");
   const egne_conv_desc& d = *dp;
+  EGNE_REQUIRE(egne::fp32_storage(d), "conv1x1_f16: split-pair / f16 storage (presplit, out_split) is not known here");
   const bool up = d.residual && d.Ho * 2 == d.H && d.Wo * 2 == d.W;
   EGNE_REQUIRE(d.kh == 1 && d.kw == 1 && d.stride == 1 && d.pad_h == 0 && d.pad_w == 0 && d.ngroups == 1 && (up || (d.Ho == d.H && d.Wo == d.W)) &&
                d.nseg >= 1 && d.nseg <= EGNE_MAXSEG && (up || !d.residual) && !d.post_scale, "conv1x1_f16: unsupported descriptor");
@@ -429,6 +430,7 @@ extern "C" int egne_conv1x1_pool2_f16x3_fwd(const egne_conv_desc* dp, const void
                                             void* stream) {
   EGNE_REQUIRE(dp && fhi && flo, "conv1x1_pool2_f16: null pointer");
   const egne_conv_desc& d = *dp;
+  EGNE_REQUIRE(egne::fp32_storage(d), "conv1x1_f16: split-pair / f16 storage (presplit, out_split) is not known here");
   EGNE_REQUIRE(d.kh == 1 && d.kw == 1 && d.stride == 1 && d.pad_h == 0 && d.pad_w == 0 && d.ngroups == 1 && d.Ho == d.H / 2 && d.Wo == d.W / 2 &&
                d.Ho > 0 && d.Wo > 0 && d.nseg >= 1 && d.nseg <= EGNE_MAXSEG && !d.residual && !d.post_scale, "conv1x1_pool2_f16: unsupported descriptor");
   EGNE_REQUIRE(d.CoutP % 32 == 0 && d.CoutP <= 96 && d.Cout_store <= d.CoutP && d.Cout_store % 4 == 0 && d.out &&

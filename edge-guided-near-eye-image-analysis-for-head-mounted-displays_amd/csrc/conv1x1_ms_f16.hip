@@ -205,6 +205,7 @@ extern "C" int egne_conv1x1_ms_f16x3_fwd(const egne_conv_desc* dp, const void* w
                                          void* stream) {
   EGNE_REQUIRE(dp && whi && wlo, "conv1x1_ms_f16: null pointer");
   const egne_conv_desc& d = *dp;
+  EGNE_REQUIRE(egne::fp32_storage(d), "conv1x1_ms_f16: split-pair / f16 storage (presplit, out_split) is not known here");
   EGNE_REQUIRE(d.kh == 1 && d.kw == 1 && d.stride == 1 && d.pad_h == 0 && d.pad_w == 0 && d.ngroups == 1 && d.Ho == d.H && d.Wo == d.W &&
                d.nseg >= 1 && d.nseg <= EGNE_MAXSEG && !d.residual && !d.post_scale, "conv1x1_ms_f16: unsupported descriptor");
   int ktot = 0;

@@ -634,6 +634,7 @@ extern "C" int egne_conv3x3_rs_f16_fwd(const egne_conv_desc* dp, const void* fhi
                                        void* stream) {
   EGNE_REQUIRE(dp && fhi && flo, "conv3x3_rs: null pointer");
   const egne_conv_desc& d = *dp;
+  EGNE_REQUIRE(egne::fp32_storage(d), "conv3x3_rs: split-pair / f16 storage (presplit, out_split) is not known here");
   static const int dbg = getenv("EGNE_RS_DBG") ? atoi(getenv("EGNE_RS_DBG")) : 0;
   static const bool m16 = getenv("EGNE_RS_M16") && atoi(getenv("EGNE_RS_M16")) == 1;
   EGNE_REQUIRE(d.kh == 3 && d.kw == 3 && d.stride == 1 && d.pad_mode == 0 && d.ngroups == 1 && d.nseg == 1 && d.pad_h == 1 &&

@@ -49,7 +49,10 @@ __device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const void* base, un
 // inside the image; a K-step adds a scalar tap offset and selects 0x80000000 for padded lanes, which the
 // buffer unit's range check turns into zeros.  Weights, residual and output use buffer instructions with
 // lane-constant offsets and scalar step offsets as well.
-template <int WGM, int WGN, int TM, int TN, bool GROUPED>
+// PS (the frame tails of the deep trunk layers whose tensors are held in channel-order split-pair storage, egne_conv_desc.out_split = 3):
+// bit 0 = split-pair output, bit 1 = split-pair input (the stored halves are copied, nothing is derived); no affine, residual
+// or post affine, one group, no split-K.  Same operands and order of products as PS = 0: bit-identical results.
+template <int WGM, int WGN, int TM, int TN, bool GROUPED, int PS = 0>
 __global__ __launch_bounds__(256) void conv_f16x3_kernel(const egne_conv_desc p, const _Float16* __restrict__ whi,
                                                          const _Float16* __restrict__ wlo, float a_scale,
                                                          float out_scale, float* __restrict__ ksplit_ws) {
@@ -89,7 +92,7 @@ __global__ __launch_bounds__(256) void conv_f16x3_kernel(const egne_conv_desc p,
     const int r = (int)(m - (long long)b * hw);
     const int oy = r / p.Wo, ox = r - oy * p.Wo;
     pb[i] = m < M ? b : -1; pyx[i] = (oy << 16) | ox;
-    roff[i] = ((((b - b0) * p.H + oy) * p.W + ox) * (int)sg.pix_stride + sg.ch_off + col4 * 4) * 4;
+    roff[i] = ((((b - b0) * p.H + oy) * p.W + ox) * (int)sg.pix_stride + sg.ch_off) * 4 + ((PS & 2) ? (col4 >> 2) * 64 + (col4 & 3) * 16 : col4 * 16);      // (split-pair input: item = 8 channels of one plane, hi planes col4 < 4)
   }
   // taps of group g that read inside the image, one bit per tap and row
   unsigned tapmask[AR];
@@ -127,7 +130,7 @@ __global__ __launch_bounds__(256) void conv_f16x3_kernel(const egne_conv_desc p,
   auto load_step = [&](int g, int tap, int c0) {
     const int dil = p.dil[g];
     const int tapoff = (((ky_n - p.pad_h) * p.W + (kx_n - p.pad_w)) * dil * (int)sg.pix_stride + c0) * 4;
-    const unsigned cbad = c0 + col4 * 4 < sg.Cp ? 0u : OOB;   // channel tail of a slice whose width is not a multiple of 32
+    const unsigned cbad = ((PS & 2) || c0 + col4 * 4 < sg.Cp) ? 0u : OOB;   // channel tail of a slice whose width is not a multiple of 32
     okmask = 0;
     st_c = c0 + col4 * 4;
 #pragma unroll
@@ -171,6 +174,10 @@ __global__ __launch_bounds__(256) void conv_f16x3_kernel(const egne_conv_desc p,
     }
 #pragma unroll
     for (int i = 0; i < AR; ++i) {
+      if constexpr ((PS & 2)) {
+        *(u32x4*)&(col4 >> 2 ? Alo : Ahi)[(rbase + 32 * i) * LDH + (col4 & 3) * 8] = ra[i];       // eight stored halves of one plane, as they are
+        continue;
+      }
       const f32x4 v = __builtin_bit_cast(f32x4, ra[i]);
       h2 h0, h1, l0, l1;                        // x * a_scale = hi + lo, plain (unpacked) VALU: split_f16.h
       egne::split2(v[0], v[1], a_scale, h0, l0);
@@ -314,6 +321,25 @@ __global__ __launch_bounds__(256) void conv_f16x3_kernel(const egne_conv_desc p,
         for (int r = 0; r < 16; ++r)
           rv[r] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rres, (int)(r0 + ((r & 3) + 8 * (r >> 2)) * rstep), 0, 0));
       }
+      if constexpr (PS & 1) {       // the pair a reader's staging would derive (split_f16.h): hi halves of the block's 32 channels, then lo
+        const unsigned s0 = nok ? (unsigned)(mrow * ostep + (p.out_ch_off + (n & ~31)) * 4 + (n & 31) * 2) : OOB;
+#pragma unroll
+        for (int r = 0; r < 16; r += 2) {
+          float v0 = acc[tm][tn][r] * out_scale + bv, v1 = acc[tm][tn][r + 1] * out_scale + bv;
+          v0 = fmaxf(v0, v0 * slope_out); v1 = fmaxf(v1, v1 * slope_out);
+          h2 hh, ll;
+          egne::split2(v0, v1, p.out_split_scale, hh, ll);
+          if (tn == 0) bad |= egne_nonfinite(v0) || egne_nonfinite(v1) || egne_nonfinite((float)hh[0]) || egne_nonfinite((float)hh[1]);
+#pragma unroll
+          for (int e = 0; e < 2; ++e) {
+            const int o = (int)(s0 + (((r + e) & 3) + 8 * ((r + e) >> 2)) * ostep);
+            const _Float16 he = hh[e], le = ll[e];      // (scalars first: a bit cast of the vector ELEMENT expression reads element 0)
+            __builtin_amdgcn_raw_buffer_store_b16(__builtin_bit_cast(unsigned short, he), rout, o, 0, 0);
+            __builtin_amdgcn_raw_buffer_store_b16(__builtin_bit_cast(unsigned short, le), rout, o + 64, 0, 0);
+          }
+        }
+        continue;
+      }
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
         float v;
@@ -434,6 +460,13 @@ int f16x3_impl(const egne_conv_desc* dp, const void* whi, const void* wlo, float
   EGNE_REQUIRE(((uintptr_t)whi & 15) == 0 && ((uintptr_t)wlo & 15) == 0 && d.out && d.Cout_store <= d.CoutP &&
                d.out_ch_off + d.Cout_store <= d.out_pix_stride, "conv_f16x3: weights / output");
   EGNE_REQUIRE(a_scale > 0.f && w_scale > 0.f, "conv_f16x3: scales");
+  // channel-order split-pair storage (out_split = 3, seg.presplit = 3): the 128 x 128 tile of a plain wide layer only, whole 32-channel blocks
+  EGNE_REQUIRE((d.seg[0].presplit == 0 || d.seg[0].presplit == 3) && (d.out_split == 0 || d.out_split == 3),
+               "conv_f16x3: storage (presplit %d, out_split %d): 0 or 3 (channel-order split pairs)", d.seg[0].presplit, d.out_split);
+  EGNE_REQUIRE((d.out_split == 0 && d.seg[0].presplit == 0) || (!allow_small && d.ngroups == 1 && d.CoutP % 128 == 0 && d.f16_products != 1 && !d.dyn_scale && !d.seg[0].scale && !d.residual &&
+                                    !d.post_scale && (d.out_split == 0 || d.out_split_scale > 0.f) && d.seg[0].Cp % 32 == 0 && d.Cout_store % 32 == 0 && d.out_ch_off % 32 == 0 &&
+                                    d.out_pix_stride % 4 == 0 && (d.seg[0].presplit == 0 || d.seg[0].ch_off % 32 == 0)),
+               "conv_f16x3: split-pair storage needs a plain three-product layer with CoutP %% 128 == 0 and whole 32-channel blocks");
   for (int g = 0; g < d.ngroups; ++g) {
     const int dd = d.dil[g];
     EGNE_REQUIRE(dd >= 1, "conv_f16x3: dilation");
@@ -464,6 +497,11 @@ int f16x3_impl(const egne_conv_desc* dp, const void* whi, const void* wlo, float
       const long long items = M * (d.CoutP / 4);
       hipLaunchKernelGGL(splitk_finish_k, dim3((unsigned)((items + 255) / 256)), dim3(256), 0, st, d, ws, sp.Z, M);
     }
+  } else if (d.out_split == 3 || d.seg[0].presplit == 3) {
+    dim3 grid((unsigned)((M + 127) / 128), (unsigned)(d.CoutP / 128));
+    if (d.seg[0].presplit == 3 && d.out_split == 3) hipLaunchKernelGGL((conv_f16x3_kernel<2, 2, 2, 2, false, 3>), grid, dim3(256), 0, st, d, h, l, a_scale, os, (float*)nullptr);
+    else if (d.seg[0].presplit == 3) hipLaunchKernelGGL((conv_f16x3_kernel<2, 2, 2, 2, false, 2>), grid, dim3(256), 0, st, d, h, l, a_scale, os, (float*)nullptr);
+    else hipLaunchKernelGGL((conv_f16x3_kernel<2, 2, 2, 2, false, 1>), grid, dim3(256), 0, st, d, h, l, a_scale, os, (float*)nullptr);
   } else if (d.CoutP % 128 == 0 && d.ngroups == 1 && big && M >= 256 * 512) {
     dim3 grid((unsigned)((M + 255) / 256), (unsigned)(d.CoutP / 128));
     hipLaunchKernelGGL((conv_f16x3_kernel<2, 2, 4, 2, false>), grid, dim3(256), 0, st, d, h, l, a_scale, os, (float*)nullptr);

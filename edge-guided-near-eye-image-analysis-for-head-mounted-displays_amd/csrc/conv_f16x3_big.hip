@@ -16,6 +16,13 @@
 //
 // M16 computes the same tile with v_mfma_f32_16x16x32_f16 (one instruction per 32-channel step and 16 x 16 block): the same
 // FLOP per cycle, but these kernels run at the power limit and the chip holds a higher clock on this shape (MI355X DVFS).
+//
+// Split-pair storage in channel order (egne_conv_desc.out_split = 3 / egne_seg.presplit = 3; 16 x 16 x 32 shape, three products): the trunk
+// tensors conv3_1 .. conv5_3 / pool3 / pool4 of the calibrated inference plan hold, per pixel and 32-channel block, [hi x32 | lo x32] halves
+// of x * s -- the very pair this kernel's staging derives from the fp32 value, computed ONCE in the producer's epilogue.  An input in that
+// storage is then staged like the weights: 16-byte pieces by LDS-DMA, the XOR swizzle of the LDS image carried by the per-lane SOURCE address
+// (taps outside the image and rows past the batch through the out-of-range offset: zeros), no registers, no VALU, no ds_write.  The operands,
+// the K order and the order of the three products are those of the converting path: the results agree bit for bit.
 #include "common.h"
 #include "split_f16.h"
 #include <cstdlib>
@@ -28,6 +35,7 @@ typedef _Float16 h8 __attribute__((ext_vector_type(8)));
 typedef _Float16 h4 __attribute__((ext_vector_type(4)));
 typedef _Float16 h2 __attribute__((ext_vector_type(2)));
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
 typedef __attribute__((address_space(3))) void* lds_ptr;
 
 namespace {
@@ -42,13 +50,16 @@ __device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const void* base, un
 // NB = 32-channel blocks per wave along N (2 -> BN = 256 with 4 waves along N, 1 -> BN = 128)
 // NP = products per multiply: 3 (hi hi + hi lo + lo hi) or 1 (hi hi: plain f16 operands; egne_conv_desc.f16_products) -- the lo halves
 // are then neither derived, stored nor read (the weight image keeps its layout: the lo chunks of a row are simply not touched)
-template <int NB, bool M16, int NP = 3>
+// PS = storage of the tensors: bit 0 split-pair (channel order) output, bit 1 split-pair input (a calibrating run measures the fp32 output of
+// a launch whose input is already split: PS = 2)
+template <int NB, bool M16, int NP = 3, int PS = 0>
 __global__ __launch_bounds__(512) void conv_f16x3_big_kernel(const egne_conv_desc p, const char* __restrict__ wimg, float a_scale,
                                                              float out_scale) {
   constexpr int BN = 128 * NB;
   constexpr int STAGE = (BM + BN) * ROWB;
   extern __shared__ __attribute__((aligned(1024))) char lds[];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = (PS & 2) ? __builtin_amdgcn_readfirstlane(tid >> 6) : tid >> 6;     // (uniform: the LDS-DMA's base goes through M0)
   const int wm = wave >> 2, wn = wave & 3;               // 2 x 4 waves; wave tile 128 x (32 * NB)
   const long long M = (long long)p.B * p.Ho * p.Wo;
   const long long m0 = (long long)blockIdx.x * BM;
@@ -65,7 +76,9 @@ __global__ __launch_bounds__(512) void conv_f16x3_big_kernel(const egne_conv_des
   // weight images: [ntile][step = chunk*T + tap][BN rows x 128 B]
   const __amdgpu_buffer_rsrc_t rw = make_rsrc(wimg + (long long)ntile * nsteps * (BN * ROWB), (unsigned)(nsteps * BN * ROWB));
 
-  // ---- A staging: thread -> 4 items (row = (tid>>3) + 64*i, float4 column c4 = tid&7) ----
+  // ---- A staging: thread -> 4 items (row = (tid>>3) + 64*i, float4 column c4 = tid&7)
+  //      split-pair input: lane -> 4 DMA pieces of 16 bytes (row = 32 wave + 8 i + (lane >> 3), LDS chunk pc = lane & 7 <- the row's chunk
+  //      c = pc ^ key(row): hi (c even) or lo (c odd) halves of channels 8 (c >> 1) .. + 7 of the block: source byte (c & 1) * 64 + (c >> 1) * 16) ----
   const int c4 = tid & 7;
   int roff[4];
   unsigned tapmask[4];
@@ -73,11 +86,13 @@ __global__ __launch_bounds__(512) void conv_f16x3_big_kernel(const egne_conv_des
     const int dil = p.dil[0];
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
-      const long long m = m0 + (tid >> 3) + 64 * i;
+      const int row_i = (PS & 2) ? 32 * wave + 8 * i + (lane >> 3) : (tid >> 3) + 64 * i;
+      const long long m = m0 + row_i;
       const int b = (int)(m / hw);
       const int r = (int)(m - (long long)b * hw);
       const int oy = r / p.Wo, ox = r - oy * p.Wo;
-      roff[i] = ((((b - b0) * p.H + oy) * p.W + ox) * (int)sg.pix_stride + sg.ch_off + c4 * 4) * 4;
+      const int lc = (lane & 7) ^ (((row_i >> 1) + 6) & 7);
+      roff[i] = ((((b - b0) * p.H + oy) * p.W + ox) * (int)sg.pix_stride + sg.ch_off) * 4 + ((PS & 2) ? (lc & 1) * 64 + (lc >> 1) * 16 : c4 * 16);
       unsigned mk = 0;
       for (int ky = 0; ky < p.kh; ++ky)
         for (int kx = 0; kx < p.kw; ++kx) {
@@ -100,13 +115,17 @@ __global__ __launch_bounds__(512) void conv_f16x3_big_kernel(const egne_conv_des
 
   u32x4 ra[4];
   int ky_n = 0, kx_n = 0, c0_n = 0;     // coordinates of the step being loaded
-  auto load_a = [&](int tap) {
+  // (split-pair input: the step's 256 rows x 128 B straight into `stage`, 32 instructions of 1 KB, four per wave)
+  auto load_a = [&](int tap, int stage) {
     const int dil = p.dil[0];
     const int tapoff = (((ky_n - p.pad_h) * p.W + (kx_n - p.pad_w)) * dil * (int)sg.pix_stride + c0_n) * 4;
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
       const bool ok = (tapmask[i] >> tap) & 1u;
-      ra[i] = __builtin_amdgcn_raw_buffer_load_b128(rin, ok ? roff[i] + tapoff : (int)OOB, 0, 0);
+      if constexpr ((PS & 2))
+        __builtin_amdgcn_raw_ptr_buffer_load_lds(rin, (lds_ptr)(lds + stage * STAGE + wave * 4096 + i * 1024), 16, ok ? roff[i] + tapoff : (int)OOB, 0, 0, 0);
+      else
+        ra[i] = __builtin_amdgcn_raw_buffer_load_b128(rin, ok ? roff[i] + tapoff : (int)OOB, 0, 0);
     }
   };
   auto dma_b = [&](int stage, int step) {
@@ -120,7 +139,7 @@ __global__ __launch_bounds__(512) void conv_f16x3_big_kernel(const egne_conv_des
   auto store_a = [&](int stage) {
     char* base = lds + stage * STAGE;
 #pragma unroll
-    for (int i = 0; i < 4; ++i) {
+    for (int i = 0; i < ((PS & 2) ? 0 : 4); ++i) {
       const f32x4 v = __builtin_bit_cast(f32x4, ra[i]);
       if constexpr (NP == 1) {
         const f32x2 t0 = {v[0] * a_scale, v[1] * a_scale}, t1 = {v[2] * a_scale, v[3] * a_scale};
@@ -160,7 +179,7 @@ __global__ __launch_bounds__(512) void conv_f16x3_big_kernel(const egne_conv_des
   const int sw = ((lr >> 1) + 6) & 7;
 
   // prologue: step 0 into stage 0
-  load_a(0);
+  load_a(0, 0);
   dma_b(0, 0);
   store_a(0);
   advance();
@@ -172,7 +191,7 @@ __global__ __launch_bounds__(512) void conv_f16x3_big_kernel(const egne_conv_des
     const int st = step & 1;
     const bool more = step + 1 < nsteps;
     if (more) {                     // loads of step+1 in flight during the MFMAs of this step
-      load_a(tap_n);
+      load_a(tap_n, st ^ 1);               // (the other stage was last read in step-1: every wave passed the barrier since)
       dma_b(st ^ 1, step + 1);
     }
     const char* base = lds + st * STAGE;
@@ -247,6 +266,58 @@ __global__ __launch_bounds__(512) void conv_f16x3_big_kernel(const egne_conv_des
   const __amdgpu_buffer_rsrc_t rout = make_rsrc(p.out + m0 * p.out_pix_stride, (unsigned)((left < BM ? left : BM) * p.out_pix_stride * 4));
   constexpr int NJ = M16 ? 1 : 4;
   bool bad = false;
+  if constexpr (PS & 1) {
+    // Split-pair output, planes in channel order.  A lane ends with channels 4 kg .. + 3 of every 16-channel block: 8 bytes per plane.  The lanes kg and
+    // kg ^ 1 (16 lanes apart) trade one piece per pair of blocks (ds_swizzle, no LDS memory), so that an even kg holds channels 8 (kg / 2) .. + 7 of the
+    // 32-channel block and an odd kg channels 16 + 8 (kg / 2) .. + 7: ONE 16-byte store per plane and lane, 64 contiguous bytes per pixel and
+    // instruction as in the fp32 form.  The stored pair is the one a reader's staging would derive from the fp32 value (split_f16.h).
+    static_assert(M16 && NP == 3, "split-pair output: 16 x 16 x 32 shape, three products");
+    const float oss = p.out_split_scale;
+    const bool odd = kg & 1;
+    const int pb = (odd ? 32 : 0) + 16 * (kg >> 1);          // byte of the lane's eight halves inside a plane
+#pragma unroll
+    for (int bp = 0; bp < NTN / 2; ++bp) {
+      const int nb = ntile * BN + wn * 32 * NB + bp * 32;      // first channel of the 32-channel block
+      const bool nok = nb < p.Cout_store;
+      const f32x4 bv0 = (p.bias && nok) ? *(const f32x4*)(p.bias + nb + 4 * kg) : (f32x4)(0.f);
+      const f32x4 bv1 = (p.bias && nok) ? *(const f32x4*)(p.bias + nb + 16 + 4 * kg) : (f32x4)(0.f);
+#pragma unroll
+      for (int tm = 0; tm < NTM; ++tm) {
+        u32x2 hi[2], lo[2];
+#pragma unroll
+        for (int q = 0; q < 2; ++q) {
+          f32x4 v;
+#pragma unroll
+          for (int e = 0; e < 4; ++e) {
+            const float t = acc[tm][2 * bp + q][e] * out_scale + (q ? bv1[e] : bv0[e]);
+            v[e] = fmaxf(t, t * slope);
+          }
+          h2 h0, h1, l0, l1;
+          egne::split2(v[0], v[1], oss, h0, l0);
+          egne::split2(v[2], v[3], oss, h1, l1);
+          if (bp == 0 && q == 0) bad |= egne_nonfinite(v[0]) || egne_nonfinite((float)h0[0]);       // lane = pixel: one channel per pixel (common.h)
+          hi[q] = u32x2{__builtin_bit_cast(unsigned, h0), __builtin_bit_cast(unsigned, h1)};
+          lo[q] = u32x2{__builtin_bit_cast(unsigned, l0), __builtin_bit_cast(unsigned, l1)};
+        }
+        // an even kg gives its piece of the second block and takes the neighbour's piece of the first; an odd kg the other way round
+        const u32x2 sh = odd ? hi[0] : hi[1], sl = odd ? lo[0] : lo[1];
+        u32x2 rh, rl;
+#pragma unroll
+        for (int e = 0; e < 2; ++e) {
+          rh[e] = (unsigned)__builtin_amdgcn_ds_swizzle((int)sh[e], 0x401f);      // lane ^ 16
+          rl[e] = (unsigned)__builtin_amdgcn_ds_swizzle((int)sl[e], 0x401f);
+        }
+        const u32x4 oh = odd ? u32x4{rh[0], rh[1], hi[1][0], hi[1][1]} : u32x4{hi[0][0], hi[0][1], rh[0], rh[1]};
+        const u32x4 ol = odd ? u32x4{rl[0], rl[1], lo[1][0], lo[1][1]} : u32x4{lo[0][0], lo[0][1], rl[0], rl[1]};
+        const int row = wm * 128 + tm * MB + lr;
+        const int o = nok ? (row * (int)p.out_pix_stride + p.out_ch_off + nb) * 4 + pb : (int)OOB;
+        __builtin_amdgcn_raw_buffer_store_b128(oh, rout, o, 0, 0);
+        __builtin_amdgcn_raw_buffer_store_b128(ol, rout, o + 64, 0, 0);
+      }
+    }
+    egne_ovf_commit(bad, p.ovf_flag);
+    return;
+  }
 #pragma unroll
   for (int tn = 0; tn < NTN; ++tn)
 #pragma unroll
@@ -307,6 +378,8 @@ extern "C" int egne_pack_conv_weight_f16img(const float* w_oihw, int Cout, int C
 
 // Same descriptor as egne_conv2d_f16x3_fwd: one input slice without fused affine, Cp % 32 == 0, stride 1, zero padding,
 // one group, no residual / post affine; d->CoutP = Cout rounded up to BN (128 or 256: CoutP % 256 == 0 selects 256).
+// d->out_split = 3 (three products only): the output in channel-order split-pair storage under d->out_split_scale; d->seg[0].presplit = 3:
+// the input in that storage, written under THIS launch's a_scale.
 extern "C" int egne_conv2d_f16x3_big_fwd(const egne_conv_desc* dp, const void* wimg, float a_scale, float w_scale, void* stream) {
   EGNE_REQUIRE(dp && wimg, "conv_f16x3_big: null pointer");
   const egne_conv_desc& d = *dp;
@@ -322,9 +395,27 @@ extern "C" int egne_conv2d_f16x3_big_fwd(const egne_conv_desc* dp, const void* w
   EGNE_REQUIRE(dd >= 1 && d.H + 2 * d.pad_h * dd - dd * (d.kh - 1) == d.Ho && d.W + 2 * d.pad_w * dd - dd * (d.kw - 1) == d.Wo,
                "conv_f16x3_big: output %dx%d inconsistent with geometry", d.Ho, d.Wo);
   EGNE_REQUIRE(((uintptr_t)wimg & 15) == 0 && a_scale > 0.f && w_scale > 0.f, "conv_f16x3_big: weights / scales");
+  EGNE_REQUIRE((g.presplit == 0 || g.presplit == 3) && (d.out_split == 0 || d.out_split == 3),
+               "conv_f16x3_big: storage (presplit %d, out_split %d): 0 or 3 (channel-order split pairs)", g.presplit, d.out_split);
   const long long M = (long long)d.B * d.Ho * d.Wo;
   const float os = 1.0f / (a_scale * w_scale);
   hipStream_t st = (hipStream_t)stream;
+  if (d.out_split == 3 || g.presplit == 3) {
+    EGNE_REQUIRE(d.f16_products != 1 && (d.out_split == 0 || (d.out_split_scale > 0.f && d.Cout_store % 32 == 0 && d.out_ch_off % 32 == 0)) &&
+                 (g.presplit == 0 || g.ch_off % 32 == 0), "conv_f16x3_big: split-pair slices are whole 32-channel blocks, three products");
+    const bool in3 = g.presplit == 3, out3 = d.out_split == 3;
+#define EGNE_BIGP_GO(NBV, PSV)                                                                                                               \
+  do {                                                                                                                                      \
+    if (!egne::raise_lds((const void*)conv_f16x3_big_kernel<NBV, true, 3, PSV>, 2 * (BM + 128 * NBV) * ROWB))                               \
+      return egne::fail(EGNE_ERR_LAUNCH, "conv_f16x3_big: cannot raise the dynamic LDS limit");                                             \
+    hipLaunchKernelGGL((conv_f16x3_big_kernel<NBV, true, 3, PSV>), dim3((unsigned)((M + BM - 1) / BM), (unsigned)(d.CoutP / (128 * NBV))),  \
+                       dim3(512), 2 * (BM + 128 * NBV) * ROWB, st, d, (const char*)wimg, a_scale, os);                                      \
+  } while (0)
+    if (d.CoutP % 256 == 0) { if (in3 && out3) EGNE_BIGP_GO(2, 3); else if (in3) EGNE_BIGP_GO(2, 2); else EGNE_BIGP_GO(2, 1); }
+    else { if (in3 && out3) EGNE_BIGP_GO(1, 3); else if (in3) EGNE_BIGP_GO(1, 2); else EGNE_BIGP_GO(1, 1); }
+#undef EGNE_BIGP_GO
+    return egne::check_launch("egne_conv2d_f16x3_big_fwd");
+  }
   static bool once = [] {
     return hipFuncSetAttribute((const void*)conv_f16x3_big_kernel<2, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024) == hipSuccess &&
            hipFuncSetAttribute((const void*)conv_f16x3_big_kernel<1, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024) == hipSuccess &&

@@ -699,6 +699,7 @@ extern "C" int egne_conv1x1_3x3_fused_f16_fwd(const egne_conv_desc* dp1, const e
                                               float a1, float w1_scale, const void* f2hi, const void* f2lo, float a2, float w2_scale,
                                               void* stream) {
   EGNE_REQUIRE(dp1 && dp2 && w1hi && w1lo && f2hi && f2lo, "conv_fused_1x1_3x3: null pointer");
+  EGNE_REQUIRE(egne::fp32_storage(*dp1) && egne::fp32_storage(*dp2), "conv_fused: split-pair / f16 storage (presplit, out_split) is not known here");
   const egne_conv_desc& d1 = *dp1;
   const egne_conv_desc& d2 = *dp2;
   EGNE_REQUIRE(d1.kh == 1 && d1.kw == 1 && d1.stride == 1 && d1.pad_h == 0 && d1.pad_w == 0 && d1.ngroups == 1 && d1.nseg >= 1 &&
@@ -797,6 +798,7 @@ extern "C" int egne_conv3x3c4_3x3_fused_f16_fwd(const egne_conv_desc* dp1, const
                                                 float a1, float w1_scale, const void* f2hi, const void* f2lo, float a2, float w2_scale,
                                                 void* stream) {
   EGNE_REQUIRE(dp1 && dp2 && c4hi && c4lo && f2hi && f2lo, "conv_fused_c4_3x3: null pointer");
+  EGNE_REQUIRE(egne::fp32_storage(*dp1) && egne::fp32_storage(*dp2), "conv_fused: split-pair / f16 storage (presplit, out_split) is not known here");
   const egne_conv_desc& d1 = *dp1;
   const egne_conv_desc& d2 = *dp2;
   EGNE_REQUIRE(d1.kh == 3 && d1.kw == 3 && d1.stride == 1 && d1.pad_h == 1 && d1.pad_w == 1 && d1.pad_mode == 0 && d1.ngroups == 1 &&

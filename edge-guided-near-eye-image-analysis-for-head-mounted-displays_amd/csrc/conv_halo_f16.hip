@@ -50,7 +50,9 @@ __device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const void* base, un
 // twice as many MFMAs (PMC: the weight ring of the <2,2,1> shape ran the vector L1 at 80 % of its 64 B/clk).
 // NP: products per multiply (egne_conv_desc.f16_products): 3 = hi hi + hi lo + lo hi; 1 = hi hi only (plain f16 operands: no lo halves
 // derived, stored, fetched or multiplied -- half the weight fragments each wave pulls from L2)
-template <int WM, int WN, int D, bool LAT, int NW, int PF = 0, bool TP = false, bool POOL = false, int NP = 3>
+// PS: the input slice is held in channel-order split-pair storage (egne_seg.presplit = 3: per pixel and 32-channel block [hi x32 | lo x32] halves of
+// x * a_scale): the stored halves are copied into the LDS image, nothing is derived (raw slices only; MSBlock convolutions of stages 3-5 of the edge network)
+template <int WM, int WN, int D, bool LAT, int NW, int PF = 0, bool TP = false, bool POOL = false, int NP = 3, bool PS = false>
 __global__ __launch_bounds__(256, 2) void conv3x3_halo_f16_kernel(const egne_conv_desc p, const _Float16* __restrict__ fhi,
                                                                const _Float16* __restrict__ flo, float a_scale,
                                                                float out_scale, int tiles_x, int tiles_y, int ntiles) {
@@ -91,7 +93,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_halo_f16_kernel(const egne_con
     for (int i = 0; i < NI; ++i) {
       const bool in = tid + 256 * i < nitems;
       hyx[i] = in ? ((S * hy) << 16) | (S * hx) : 0x7fff7fff;
-      roff[i] = ((S * hy * rstep + S * hx * cstep) * (int)sg.pix_stride + c4 * 4) * 4;
+      roff[i] = (S * hy * rstep + S * hx * cstep) * (int)sg.pix_stride * 4 + (PS ? (c4 >> 2) * 64 + (c4 & 3) * 16 : c4 * 16);      // (PS: item = 8 channels of one plane: hi planes c4 < 4, lo 4 .. 7)
       hx += 32;
       if (hx >= HWd) { hx -= HWd; ++hy; }
     }
@@ -128,7 +130,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_halo_f16_kernel(const egne_con
   f32x4 st_sc = {1.f, 1.f, 1.f, 1.f}, st_sh = {0.f, 0.f, 0.f, 0.f};
   unsigned st_cmask = 0;
   auto load_chunk = [&](int c0) {
-    const bool cok = c0 + c4 * 4 < Cp;
+    const bool cok = PS || c0 + c4 * 4 < Cp;       // (PS: whole 32-channel blocks)
     st_cmask = cok ? 0u : OOB;
     if (sg.scale) {
       st_sc = *(const f32x4*)(cok ? sg.scale + (long long)stage_b * Cp + c0 + c4 * 4 : egne_zero_page);
@@ -157,6 +159,10 @@ __global__ __launch_bounds__(256, 2) void conv3x3_halo_f16_kernel(const egne_con
         const f32x4 v = __builtin_bit_cast(f32x4, st[i]);
         // x*a_scale = hi + lo, two elements per (packed) instruction
         const int o = lofs0 + i * 32 * LDH;
+        if constexpr (PS) {       // eight stored halves of one plane, as they are
+          *(u32x4*)&(c4 >> 2 ? Alo : Ahi)[(tid >> 3) * LDH + (c4 & 3) * 8 + i * 32 * LDH] = st[i];
+          continue;
+        }
         if constexpr (NP == 1) {
           float t0, t1, t2, t3;
           asm("v_mul_f32_e32 %0, %1, %2" : "=v"(t0) : "s"(a_scale), "v"(v[0]));
@@ -390,7 +396,7 @@ __global__ void pack_weight_f16frag_k(const float* __restrict__ w, int Cout, int
   }
 }
 
-template <int WM, int WN, int D, bool LAT, int NW = 1, int PF = 0, bool TP = false, int NP = 3>
+template <int WM, int WN, int D, bool LAT, int NW = 1, int PF = 0, bool TP = false, int NP = 3, bool PS = false>
 int launch_hf_tp(const egne_conv_desc& d, const _Float16* fhi, const _Float16* flo, float a_scale, float os, hipStream_t st) {
   constexpr int TH = (4 / NW) * WM;
   const int S = LAT ? d.dil[0] : 1;
@@ -401,22 +407,22 @@ int launch_hf_tp(const egne_conv_desc& d, const _Float16* fhi, const _Float16* f
   const int ntiles = tiles_x * tiles_y * d.B * S * S, ny = d.CoutP / (32 * WN * NW);
   int gx = (256 * 2 + ny - 1) / ny;
   if (gx > ntiles) gx = ntiles;
-  hipLaunchKernelGGL((conv3x3_halo_f16_kernel<WM, WN, D, LAT, NW, PF, TP, false, NP>), dim3(gx, ny), dim3(256), lds, st, d, fhi, flo, a_scale, os, tiles_x,
+  hipLaunchKernelGGL((conv3x3_halo_f16_kernel<WM, WN, D, LAT, NW, PF, TP, false, NP, PS>), dim3(gx, ny), dim3(256), lds, st, d, fhi, flo, a_scale, os, tiles_x,
                      tiles_y, ntiles);
   return egne::check_launch("egne_conv3x3_halo_f16_fwd");
 }
 
 // Walk the image transposed when 8 x 32 tiles fit it better that way (dilation 8 on 240x320: 30 x 40 lattice points per
 // phase = 8 wide tiles at 59 % fill or 5 tall tiles at 94 %; plain 60x80 and 30x40 maps likewise).  D = 1 shapes only.
-template <int WM, int WN, int D, bool LAT, int NW = 1, int PF = 0, int NP = 3>
+template <int WM, int WN, int D, bool LAT, int NW = 1, int PF = 0, int NP = 3, bool PS = false>
 int launch_hf(const egne_conv_desc& d, const _Float16* fhi, const _Float16* flo, float a_scale, float os, hipStream_t st) {
   constexpr int TH = (4 / NW) * WM;
   const int S = LAT ? d.dil[0] : 1;
   auto ntile = [&](int vh, int vw) { return ((((vw + S - 1) / S) + TW - 1) / TW) * ((((vh + S - 1) / S) + TH - 1) / TH); };
   static const bool tall_ok = [] { const char* e = getenv("EGNE_SHALO_TALL"); return !e || e[0] != '0'; }();
   if (D == 1 && NW == 1 && PF == 0 && tall_ok && ntile(d.W, d.H) < ntile(d.H, d.W))
-    return launch_hf_tp<WM, WN, (D == 1 && NW == 1 && PF == 0 ? D : 1), LAT, (D == 1 && NW == 1 && PF == 0 ? NW : 1), 0, true, NP>(d, fhi, flo, a_scale, os, st);
-  return launch_hf_tp<WM, WN, D, LAT, NW, PF, false, NP>(d, fhi, flo, a_scale, os, st);
+    return launch_hf_tp<WM, WN, (D == 1 && NW == 1 && PF == 0 ? D : 1), LAT, (D == 1 && NW == 1 && PF == 0 ? NW : 1), 0, true, NP, PS>(d, fhi, flo, a_scale, os, st);
+  return launch_hf_tp<WM, WN, D, LAT, NW, PF, false, NP, PS>(d, fhi, flo, a_scale, os, st);
 }
 
 }  // namespace
@@ -460,6 +466,11 @@ extern "C" int egne_conv3x3_halo_f16_fwd(const egne_conv_desc* dp, const void* f
   hipStream_t st = (hipStream_t)stream;
   const _Float16* h = (const _Float16*)fhi;
   const _Float16* l = (const _Float16*)flo;
+  // a slice in channel-order split-pair storage (presplit = 3, written under this launch's a_scale): the plain dilation-1 shape of a raw 32-output layer
+  EGNE_REQUIRE(g.presplit == 0 || (g.presplit == 3 && d.dil[0] == 1 && d.CoutP == 32 && !g.scale && !d.dyn_scale && d.f16_products != 1 && !d.pool_out &&
+                                   g.Cp % 32 == 0 && g.ch_off % 32 == 0),
+               "conv_halo_f16: presplit %d: 0, or 3 on a raw slice of whole 32-channel blocks (dilation 1, CoutP 32, three products)", g.presplit);
+  if (g.presplit == 3) return launch_hf<2, 1, 1, false, 1, 0, 3, true>(d, (const _Float16*)fhi, (const _Float16*)flo, a_scale, os, st);
   const bool w2 = d.CoutP % 64 == 0;   // wider layers: several 64-wide N tiles along grid.y, each re-stages the halo
   // opt-in: measured equal to the <2,2,1> shape (the rolled tap loop gives back what the halved weight traffic gains)
   static const int nw2 = [] { const char* e = getenv("EGNE_SHALO_NW2"); return e ? atoi(e) : 0; }();

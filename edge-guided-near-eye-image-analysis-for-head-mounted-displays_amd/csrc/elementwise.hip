@@ -313,6 +313,55 @@ __global__ void maxpool2_f16_k(const _Float16* __restrict__ x, long long xs, int
   }
 }
 
+// the same pooling over a slice in channel-order split-pair storage (egne_conv_desc.out_split = 3: per pixel and 32-channel block 32 hi halves, then 32
+// lo halves of x * s; strides and offsets in units of 4 bytes).  hi + lo is exact in fp32, so the window is compared on that sum and the winner's PAIR is
+// written; two neighbours of a rounding midpoint of hi can have equal sums and different pairs -- the larger value is then the one with the larger hi.
+// Bit-equal to splitting the pooled fp32 tensor.  Four channels (8 + 8 bytes) per thread.
+__global__ void maxpool2_split_k(const char* __restrict__ x, long long xs, int xo, char* __restrict__ y, long long ys,
+                                 int yo, int B, int H, int W, int Ho, int Wo, int stride, int Cp) {
+  typedef _Float16 h4_ __attribute__((ext_vector_type(4)));
+  const unsigned nv = Cp >> 2;
+  const unsigned t = blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= (unsigned)Wo * nv) return;
+  const int ox = (int)(t / nv), c = (int)(t - ox * nv) * 4;
+  const int b = blockIdx.z;
+  const int x0 = ox * stride, x1 = x0 + 1 < W ? x0 + 1 : x0;
+  const int cb = (c & ~31) * 4 + (c & 31) * 2;                 // byte offset of the four hi halves inside the pixel's slice
+  const char* s = x + (((long long)b * H * W) * xs + xo) * 4 + cb;
+  h4_ vh[4][4], vl[4][4];
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const int oy = blockIdx.y * 4 + j;
+    const int y0 = oy < Ho ? oy * stride : 0, y1 = y0 + 1 < H ? y0 + 1 : y0;
+    const long long o[4] = {((long long)y0 * W + x0) * xs * 4, ((long long)y0 * W + x1) * xs * 4, ((long long)y1 * W + x0) * xs * 4,
+                            ((long long)y1 * W + x1) * xs * 4};
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      vh[j][k] = *(const h4_*)(s + o[k]);
+      vl[j][k] = *(const h4_*)(s + o[k] + 64);
+    }
+  }
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const int oy = blockIdx.y * 4 + j;
+    if (oy < Ho) {
+      h4_ rh = vh[j][0], rl = vl[j][0];
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        float best = (float)rh[e] + (float)rl[e];
+#pragma unroll
+        for (int k = 1; k < 4; ++k) {
+          const float v = (float)vh[j][k][e] + (float)vl[j][k][e];
+          if (v > best || (v == best && (float)vh[j][k][e] > (float)rh[e])) { best = v; rh[e] = vh[j][k][e]; rl[e] = vl[j][k][e]; }
+        }
+      }
+      char* d = y + ((((long long)b * Ho + oy) * Wo + ox) * ys + yo) * 4 + cb;
+      *(h4_*)d = rh;
+      *(h4_*)(d + 64) = rl;
+    }
+  }
+}
+
 template <typename T>
 __global__ void upsample2x_k(const T* __restrict__ x, long long xs, int xo, T* __restrict__ y, long long ys,
                              int yo, int B, int H, int W, int Cp) {
@@ -643,6 +692,19 @@ extern "C" int egne_maxpool2_f16(const void* x, int64_t xs, int xo, void* y, int
   hipLaunchKernelGGL(maxpool2_f16_k, dim3((Wo * (Cp / 8) + 255) / 256, (Ho + 3) / 4, B), dim3(256), 0, (hipStream_t)stream, (const _Float16*)x,
                      (long long)xs, xo, (_Float16*)y, (long long)ys, yo, B, H, W, Ho, Wo, stride, Cp);
   return egne::check_launch("egne_maxpool2_f16");
+}
+
+extern "C" int egne_maxpool2_split(const void* x, int64_t xs, int xo, void* y, int64_t ys, int yo, int B, int H, int W,
+                                   int Ho, int Wo, int stride, int Cp, void* stream) {
+  EGNE_REQUIRE(x && y && Cp > 0 && Cp % 32 == 0 && xs % 4 == 0 && ys % 4 == 0 && xo % 32 == 0 && yo % 32 == 0 && ((uintptr_t)x & 15) == 0 &&
+               ((uintptr_t)y & 15) == 0 && xo + Cp <= xs && yo + Cp <= ys, "maxpool2_split: bad slices (whole 32-channel blocks)");
+  EGNE_REQUIRE(stride == 1 || stride == 2, "maxpool2_split: stride %d", stride);
+  auto osz = [&](int n) { const int a = (n - 2 + stride - 1) / stride + 1, b_ = (n - 1) / stride + 1; return a < b_ ? a : b_; };
+  EGNE_REQUIRE(B > 0 && H >= 2 && W >= 2 && Ho == osz(H) && Wo == osz(W), "maxpool2_split: output %dx%d != %dx%d", Ho, Wo, osz(H), osz(W));
+  EGNE_REQUIRE(Ho <= 65535 && B <= 65535, "maxpool2_split: grid limits");
+  hipLaunchKernelGGL(maxpool2_split_k, dim3((Wo * (Cp / 4) + 255) / 256, (Ho + 3) / 4, B), dim3(256), 0, (hipStream_t)stream, (const char*)x,
+                     (long long)xs, xo, (char*)y, (long long)ys, yo, B, H, W, Ho, Wo, stride, Cp);
+  return egne::check_launch("egne_maxpool2_split");
 }
 
 extern "C" int egne_maxpool2(const float* x, int64_t xs, int xo, float* y, int64_t ys, int yo, int B, int H, int W,

@@ -409,6 +409,7 @@ extern "C" int egne_msblock_dil_scores_f16_fwd(const egne_conv_desc* dp, const v
                      hipFuncSetAttribute((const void*)msblock_dil_kernel<4, 8, 12, 4, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) == hipSuccess;
   if (!once) return egne::fail(EGNE_ERR_LAUNCH, "msblock_dil: cannot raise the dynamic LDS limit to %zu", lds);
   const float os = 1.0f / (a_scale * w_scale), inv_a = 1.0f / a_scale;
+  EGNE_REQUIRE((g.presplit == 0 || g.presplit == 1) && d.out_split == 0, "msblock_dil: presplit %d / out_split %d: the input is fp32 or split-pair storage 1, the output fp32", g.presplit, d.out_split);
   const bool ps = g.presplit != 0;
   // split-pair input: the residual must be that same slice (bdcn_new.py:54 adds `o` itself), whole 32-channel blocks
   EGNE_REQUIRE(!ps || (d.residual == g.ptr && d.res_pix_stride == g.pix_stride && d.res_ch_off == g.ch_off && g.ch_off % 32 == 0),

@@ -130,7 +130,7 @@ def _ptr(t, elem_off=0):
 class Piece:
     """A channel slice [off, off+Cp) of an NHWC fp32 buffer (optionally starting at sample n0)."""
 
-    __slots__ = ("buf", "off", "C", "Cp", "n0", "scale", "shift", "act_in", "nograd", "presplit", "norm_fuse", "f16s")
+    __slots__ = ("buf", "off", "C", "Cp", "n0", "scale", "shift", "act_in", "nograd", "presplit", "norm_fuse", "f16s", "split3")
 
     def __init__(self, buf, off, C_, Cp=None, n0=0):
         self.buf, self.off, self.C, self.Cp, self.n0 = buf, int(off), int(C_), int(Cp or pad8(C_)), int(n0)
@@ -139,6 +139,7 @@ class Piece:
         self.nograd = False
         self.presplit = None    # a SplitScale: the slice is held in split-pair storage (egne_conv_desc.out_split), see Plan.conv
         self.f16s = None        # a SplitScale: the slice is held as F16 halves of x * value (egne_conv_desc.out_split = 2; Plan.buf16)
+        self.split3 = None      # a SplitScale: the slice is held in CHANNEL-ORDER split-pair storage (egne_conv_desc.out_split = 3), see PRESPLIT_TRUNK
         # training plans: the InstanceNorm backward of this tensor's normalised readers joins its gradient where its PRODUCING convolution
         # masks it (egne_act_norm_bwd; set by the plan builder on tensors whose producer is a convolution of the plan, Plan._pending)
         self.norm_fuse = False
@@ -180,6 +181,10 @@ class NeedsFp32Storage(Exception):
 
 F16_STORAGE = os.environ.get("EGNE_F16_STORAGE", "1") != "0"   # plain-f16 plans (f16_products = 1): conv1_1 / conv1_2 / pool1 of the edge network as f16 tensors
 F16_STORAGE_DEEP = os.environ.get("EGNE_F16_STORAGE_DEEP", "1") != "0"   # ... and conv3_1 .. conv5_3, pool3 / pool4 (the deep trunk kernel stages both operands by LDS-DMA)
+# calibrated three-product inference plan of the edge network: conv3_1 .. conv5_3, pool3 / pool4 in channel-order split-pair storage (out_split = 3), written
+# once by their producers under the pre-scale their readers use (the power of two of the tensor's own maximum); deep trunk kernel (activations by LDS-DMA),
+# its frame tail, the MSBlock 3x3 and the pooling read the stored pairs.  Same operands in the same order: bit-identical to the fp32-tensor plan.
+PRESPLIT_TRUNK = os.environ.get("EGNE_PRESPLIT_TRUNK", "1") != "0"
 PRESPLIT = os.environ.get("EGNE_PRESPLIT", "1") != "0"    # MSBlock: `o` written in split-pair storage by its producer (resident-weights 3x3)
 # Position p of a 32-channel block in split-pair storage holds channel 16 * ((p >> 2) & 1) + 4 * (p >> 3) + (p & 3): the producer's
 # lanes end with channels {4 kg .. 4 kg + 3} and {16 + 4 kg .. 16 + 4 kg + 3} of a pixel (transposed 16x16x32 product) and store them as
@@ -644,6 +649,7 @@ class Plan:
         self.pre = []       # python callables run before the launches (BN folding etc.)
         self.meta = []      # per call: (kernel family, algorithmic FLOPs) for bench.py's roofline
         self.wscale_refs = []   # (call index, argument index, layer, attribute): weight-pack scales baked into launch arguments
+        self.post_cal3 = {}  # call index of a layer's LAST launch -> ([(call index, descriptor)], output Piece, its SplitScale, pixels): split-pair (3) outputs, see _split3_out
         self.post_cal = {}  # call index -> (descriptor, f16 output Piece, its SplitScale, pixels): scale of an f16 output re-measured behind the calibrating launch
         self.cal = {}       # call index -> (index of the a_scale argument, raw input Pieces, pixels): split-f16 pre-scale calibration
         self.calibrated = False
@@ -1029,6 +1035,8 @@ class Plan:
             q.seg_affine[i] = int(p.scale is not None)
         p0 = pieces[0]
         q.seg_planar, q.seg_presplit = int(isinstance(p0, PlanarPiece)), int(getattr(p0, "presplit", None) is not None)
+        if getattr(p0, "split3", None) is not None:
+            q.seg_presplit = 3
         q.Cout, q.Cout_store = layer.Cout, layer.Cout_store
         q.dst_Cp, q.dst_ch_off, q.dst_pix_stride = dst.Cp, dst.off, dst.stride
         q.act, q.has_post, q.has_residual = layer.act, int(layer.post is not None), int(residual is not None)
@@ -1308,6 +1316,19 @@ class Plan:
             big_tail = 0                      # (the flat kernel behind a ragged last round reads and writes fp32)
         if any16 and not ((shalo and rs and not (big or ms1x1 or s1x1 or msdil or lattice)) or (smallcin and c4h and not big) or (big and big1)):
             raise NeedsFp32Storage(name)      # only the resident-weights 3x3, the first-layer kernel and the plain-f16 deep trunk kernel know f16 storage
+        in3, out3 = getattr(pieces[0], "split3", None), dst.split3
+        if in3 is not None or out3 is not None:
+            # channel-order split-pair storage: written by the deep trunk kernel and its frame tail, read by them and by the plain halo kernel (32 outputs)
+            halo3 = (shalo and not rs and not lattice and not msdil and not big and not ms1x1 and not s1x1 and out3 is None and layer.dils[0] == 1
+                     and layer.sfrag_coutp() == 32 and not stats and getattr(self, "_pool_req", None) is None)
+            if not ((big or halo3) and not (big and big1) and self.f16_products != 1 and CALIBRATE and not self.dyn_scales and raw and not self.train
+                    and pieces[0].Cp % 32 == 0 and pieces[0].off % 32 == 0 and (out3 is None or (int(d.Cout_store) % 32 == 0 and dst.off % 32 == 0))):
+                raise NeedsFp32Storage(name)
+            if in3 is not None:
+                d.seg[0].presplit = 3
+                # the storage scale IS the launch's a_scale (argument 2 of the deep trunk kernel, 3 of the flat and halo kernels)
+                cal2 = (lambda args, vmax, in3=in3: args[:2] + (in3.value,) + args[3:], [], 0)
+                cal3 = (lambda args, vmax, in3=in3: args[:3] + (in3.value,) + args[4:], [], 0)
         if big and big_tail:
             # two launches over disjoint frame ranges: [0, B - tail) on the 256-wide kernel, the rest on the 128x128 kernel
             layer.ensure_packed(self.device)
@@ -1325,6 +1346,8 @@ class Plan:
                       flops=flops * b1 / B, kind="conv_f16x3:big", cal=cal2, ws=[(3, layer, "w_scale_big")])
             self._add(self.L.egne_conv2d_f16x3_fwd, (C.byref(d2), layer.whi.data_ptr(), layer.wlo.data_ptr(), F16X3_ASCALE, layer.w_scale),
                       name + ".tail", flops=flops * big_tail / B, kind="conv_f16x3:flat", cal=cal3, ws=[(4, layer, "w_scale")])
+            if out3 is not None:
+                self._split3_out([(len(self.calls) - 2, d), (len(self.calls) - 1, d2)], dst, B * Ho * Wo)
         elif big:
             if any16:
                 if not (CALIBRATE and not self.dyn_scales and raw):
@@ -1336,6 +1359,8 @@ class Plan:
             self._add(self.L.egne_conv2d_f16_big1_fwd if big1 else self.L.egne_conv2d_f16x3_big_fwd,
                       (C.byref(d), (layer.wimg1 if big1 else layer.wimg).data_ptr(), F16X3_ASCALE, layer.w_scale_big), name,
                       flops=flops, kind="conv_f16x3:big", cal=cal2, ws=[(3, layer, "w_scale_big")])
+            if out3 is not None:
+                self._split3_out([(len(self.calls) - 1, d)], dst, B * Ho * Wo)
         elif ms1x1:
             d.Ktot, d.CoutP = layer.m1_ktot, layer.m1_coutp
             self._add(self.L.egne_conv1x1_ms_f16x3_fwd, (C.byref(d), layer.m1hi.data_ptr(), layer.m1lo.data_ptr(), F16X3_ASCALE,
@@ -1500,6 +1525,15 @@ class Plan:
             return ai(args, vmax) if callable(ai) else args[:ai] + (_a_scale_for(vmax),) + args[ai + 1:]
         self.post_cal[len(self.calls)] = (d, dst, fs, npix)
         return (cal_out, pcs, npx)
+
+    def _split3_out(self, launches, dst, npix):
+        """dst is held in channel-order split-pair storage (Piece.split3): out_split = 3 under the pre-scale its readers would take from the fp32 tensor,
+        _a_scale_for(max |x|).  The calibrating run therefore first lets the layer's launches (deep trunk kernel, frame tail) write plain fp32 into the same
+        bytes, measures that tensor exactly as a reader's calibration would, and runs them again with the storage on (Plan._run_calibrating)."""
+        ss = dst.split3
+        for _, dd in launches:
+            dd.out_split, dd.out_split_scale = 3, ss.value
+        self.post_cal3[launches[-1][0]] = (launches, dst, ss, npix)
 
     def _f16_in(self, d, fin, cal, ai):
         """pieces[0] is held as f16 (Piece.f16s = fin): presplit = 2 and the launch's a_scale argument (index ``ai``) IS the storage scale --
@@ -2213,7 +2247,10 @@ class Plan:
         assert src.Cp == dst.Cp
         f16 = getattr(src, "f16s", None) is not None
         assert (not f16 and dst.f16s is None) or dst.f16s is src.f16s, "%s: a pooled f16 slice keeps its input's storage scale" % name
-        self._add(self.L.egne_maxpool2_f16 if f16 else self.L.egne_maxpool2, (src.ptr, src.stride, src.off, dst.ptr, dst.stride, dst.off, B, H, W, Ho, Wo,
+        s3 = getattr(src, "split3", None)
+        # (a pooled split-pair slice keeps its input's pairs, so its scale: the maximum of a non-negative tensor survives the pooling, every pixel is in a window)
+        assert dst.split3 is s3 and not (f16 and s3 is not None), "%s: a pooled split-pair slice keeps its input's storage scale" % name
+        self._add(self.L.egne_maxpool2_split if s3 is not None else self.L.egne_maxpool2_f16 if f16 else self.L.egne_maxpool2, (src.ptr, src.stride, src.off, dst.ptr, dst.stride, dst.off, B, H, W, Ho, Wo,
                                                                             stride, src.Cp), name, kind="maxpool2")
         return Ho, Wo
 
@@ -2390,6 +2427,9 @@ def _run_calibrating(self, st):
     from it.  One small sync per such launch, paid once; later runs replay the stored scales with no sync."""
     import math
     mx = torch.zeros(1, dtype=torch.int32, device=self.device)
+    for launches, _, _, _ in self.post_cal3.values():      # split-pair (3) outputs are first written as fp32 and measured as such
+        for _, dd in launches:
+            dd.out_split = 0
     for i, (fn, args, name) in enumerate(self.calls):
         ent = self.cal.get(i)
         if ent is not None:
@@ -2422,6 +2462,19 @@ def _run_calibrating(self, st):
             if new != fs.value:
                 fs.value = d.out_split_scale = new
                 _lib.check(fn(*args, st), name)
+        pc = self.post_cal3.get(i)
+        if pc is not None:        # a split-pair (3) output: the fp32 tensor is complete -- its readers' pre-scale from its maximum, then stored as pairs
+            launches, dst, ss, npix = pc
+            mx.zero_()
+            _lib.check(self.L.egne_absmax(dst.ptr, dst.stride, dst.off, dst.Cp, npix, mx.data_ptr(), st), "absmax")
+            v = float(mx.view(torch.float32).item())
+            if not math.isfinite(v):
+                raise RuntimeError("non-finite activations leave %s (max |x| = %r)" % (name, v))
+            ss.vmax, ss.value = v, _a_scale_for(v)
+            for j, dd in launches:
+                dd.out_split, dd.out_split_scale = 3, ss.value
+                fj, aj, nj = self.calls[j]
+                _lib.check(fj(*aj, st), nj)
     self.calibrated = True
 
 

@@ -51,7 +51,10 @@ typedef struct {
   int32_t presplit;     /* 1: the slice is held in SPLIT-PAIR storage (see egne_conv_desc.out_split), written with the scale that is
                          * passed as this launch's a_scale; honoured by egne_msblock_dil(_scores)_f16_fwd only, 0 everywhere else.
                          * 2: the slice is held as F16 (out_split = 2 of its producer; ptr at halfs, pix_stride / ch_off in halfs, multiples
-                         * of 8), written with this launch's a_scale: egne_conv3x3_rw_f16_fwd with f16_products = 1 only */
+                         * of 8), written with this launch's a_scale: egne_conv3x3_rw_f16_fwd with f16_products = 1 only.
+                         * 3: the slice is held in split-pair storage in CHANNEL order (out_split = 3 of its producer), written with this launch's
+                         * a_scale: egne_conv2d_f16x3_big_fwd, egne_conv2d_f16x3_fwd (128-wide layers), egne_conv3x3_halo_f16_fwd (32 outputs,
+                         * dilation 1).  Every other split-f16 entry point rejects the value. */
 } egne_seg;
 
 /*
@@ -130,7 +133,14 @@ typedef struct {
    * `pool_out` then point at halfs, strides and offsets count halfs (slices on multiples of 8).  A plain-f16 consumer rounds its operand to
    * exactly this value while staging it (f16(x a_scale), a_scale = s), so the stored tensor carries everything the consumer would have
    * kept at half the bytes: conv1_1 / conv1_2 / pool1 of the frozen edge network next to a bf16-storage training plan
-   * (vgg16_c.py:66-70 under utils.py:646).  Consumers read it through seg.presplit = 2 with a_scale = s. */
+   * (vgg16_c.py:66-70 under utils.py:646).  Consumers read it through seg.presplit = 2 with a_scale = s.
+   * out_split = 3 (egne_conv2d_f16x3_big_fwd, egne_conv2d_f16x3_fwd on 128-wide layers; three products): split-pair storage with both planes in
+   * CHANNEL order -- position p of either plane holds channel p of the block (the deep trunk kernel's lanes trade halves so that each stores 16 bytes per plane).  The wide trunk tensors
+   * conv3_1 .. conv5_3, pool3, pool4 of the calibrated inference plan of the edge network (vgg16_c.py:72-88): their readers stage an element 9-18
+   * times and would derive the same pair every time; with this storage they copy it (the deep trunk kernel by LDS-DMA) and multiply the same
+   * operands in the same order as over the fp32 tensor, so the results are bit-identical.  s is the pre-scale the readers would use:
+   * the power of two that puts max |x| of the tensor in [1024, 2048).  Read through seg.presplit = 3 with a_scale = s; pooled by
+   * egne_maxpool2_split. */
   int32_t out_split;
   float out_split_scale;      /* s > 0, a power of two */
   /* Optional (every split-f16 entry point): sticky overflow word.  The kernel sets bit 0 when a value it stores is not finite --
@@ -366,6 +376,12 @@ int egne_maxpool2(const float* x, int64_t xs, int xo, float* y, int64_t ys, int 
  * the storage scale, so the output is held under the input's scale (pool3 / pool4 of vgg16_c.py:76-82 in a plain-f16 plan). */
 int egne_maxpool2_f16(const void* x, int64_t xs, int xo, void* y, int64_t ys, int yo, int B, int H, int W, int Ho, int Wo, int stride,
                       int Cp, void* stream);
+
+/* The same pooling over a slice in channel-order split-pair storage (egne_conv_desc.out_split = 3; strides / offsets in units of 4 bytes, whole
+ * 32-channel blocks): the window is compared on hi + lo (exact in fp32), the winner's pair is written, on equal sums the pair with the larger hi --
+ * bit-equal to the split of the pooled fp32 tensor under the same scale (pool3 / pool4 of vgg16_c.py:76-82 in the calibrated inference plan). */
+int egne_maxpool2_split(const void* x, int64_t xs, int xo, void* y, int64_t ys, int yo, int B, int H, int W, int Ho, int Wo, int stride,
+                        int Cp, void* stream);
 
 /* F.interpolate(bilinear, scale_factor=2, align_corners=False) (models/RITnet_v2.py:80-83). */
 int egne_upsample2x(const float* x, int64_t xs, int xo, float* y, int64_t ys, int yo,
@@ -883,7 +899,8 @@ typedef struct {
   int64_t seg_pix_stride[EGNE_MAXSEG];
   int32_t seg_affine[EGNE_MAXSEG];/* 1: per-(n, c) affine (+ activation) applied on load (egne_seg.scale) */
   int32_t seg_planar;             /* the one slice is an NCHW tensor read in place (first layer) */
-  int32_t seg_presplit;           /* the one slice is in split-pair storage (egne_seg.presplit) */
+  int32_t seg_presplit;           /* the one slice is in split-pair storage: the value of egne_seg.presplit (1, or 3 = channel order; 3 changes no choice:
+                                   * the deep trunk, flat and halo kernels read it in place of the fp32 tensor) */
   int32_t Cout;                   /* logical output channels of ONE group */
   int32_t Cout_store;             /* channels the layer stores (0: Cout rounded up to 8) */
   int32_t dst_Cp, dst_ch_off; int64_t dst_pix_stride;
