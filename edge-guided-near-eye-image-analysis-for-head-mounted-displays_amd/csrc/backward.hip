@@ -99,6 +99,8 @@ __global__ __launch_bounds__(256) void loss_bwd_k(const egne_loss_desc d, const 
     } else if (j == 5 || j == 6) {
       g = 10.f * gscale * sgn(d.elOut[b * 10 + j] - cf[16 + (j - 5)]) / (2.f * nabs);
     }
+    // no mask in the batch: pred_c's iris row is a copy of elOut[:, 5:7] (RITnet_v2.py:404), its upstream gradient belongs to elOut
+    if (d.g_pred_c && !(nmask > 0.f) && (j == 5 || j == 6)) g += d.g_pred_c[b * 4 + (j - 5)];
     if (d.g_elOut_up) g += d.g_elOut_up[b * 10 + j];
     g_elOut[b * 10 + j] = g;
   }

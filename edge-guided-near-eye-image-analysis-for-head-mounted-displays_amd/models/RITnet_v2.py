@@ -144,9 +144,7 @@ class _ESFFunction(torch.autograd.Function):
                 up[:, 2:5] += ge[:, 2:5]
                 up[:, 7:10] += ge[:, 7:10]
                 # no mask in the batch: the iris centre of elPred is a copy of elOut[:, 5:7] (RITnet_v2.py:404), else the soft-argmax
-                # of the logits; out_terms[5] = number of samples with a mask, read on the device
-                has_mask = (pl.terms[5] > 0).to(torch.float32)
-                up[:, 5:7] += (1.0 - has_mask) * ge[:, 0:2]
+                # of the logits; egne_loss_bwd routes g_pred_c's iris row accordingly (out_terms[5], read on the device)
                 keep.append(torch.cat((ge[:, 0:2], ge[:, 5:7]), 1).contiguous())
                 ld.g_pred_c = keep[-1].data_ptr()
             keep.append(up)

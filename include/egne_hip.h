@@ -458,8 +458,9 @@ typedef struct {
   /* egne_loss_bwd only, all optional (round 5): gradients a caller back-propagates through the OUTPUTS next to the loss
    * (models/RITnet_v2.py:334-354 returns op, elPred, elOut with grad): added to what the loss terms themselves give. */
   const float* g_op_nchw;      /* [B,3,H,W] upstream gradient w.r.t. the logits */
-  const float* g_pred_c;       /* [B,2,2] upstream gradient w.r.t. pred_c (iris, pupil soft-argmax centres; the iris row is ignored when
-                                  no sample of the batch has a mask: pred_c's iris row is then a copy of elOut[:,5:7], RITnet_v2.py:404) */
+  const float* g_pred_c;       /* [B,2,2] upstream gradient w.r.t. pred_c (iris, pupil soft-argmax centres; when no sample of the batch
+                                  has a mask pred_c's iris row is a copy of elOut[:,5:7], RITnet_v2.py:404: its gradient is then added
+                                  to g_elOut[:,5:7] instead of the logits) */
   const float* g_elOut_up;     /* [B,10] upstream gradient w.r.t. elOut */
 } egne_loss_desc;
 int64_t egne_loss_workspace_floats(int B, int H, int W);
