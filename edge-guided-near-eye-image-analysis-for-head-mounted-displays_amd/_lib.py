@@ -194,6 +194,7 @@ SIGNATURES = {
     "egne_pack_conv_weight_dgrad": (i32, [vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp, vp]),
     "egne_ellipse_fit": (i32, [vp, i32, vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp]),
     "egne_ellipse_init_from_pred": (i32, [vp, i32, i32, i32, vp, vp, vp, vp]),
+    "egne_ellipse_iou_counts": (i32, [vp, i32, vp, vp, i32, i32, i32, vp, vp, vp, vp, i32, vp]),
     "egne_last_error": (C.c_char_p, []),
     "egne_version": (i32, []),
     "egne_sizeof": (i32, [i32]),

@@ -125,6 +125,103 @@ __device__ __forceinline__ unsigned row_pop(const unsigned* rowbits, int x0, int
   return n;
 }
 
+// Bit-packs the class-k pixels of rows first, first + step, ... of frame m into bits[H][wpr] and returns how many there are (wave-uniform:
+// ballots); the waves that share a mask pack its rows in turn.
+__device__ __forceinline__ unsigned pack_mask_rows(const long long* __restrict__ m, int k, int H, int W, unsigned* bits, int wpr, int lane,
+                                                   int first, int step) {
+  unsigned cnt = 0;
+  for (int y = first; y < H; y += step)
+    for (int x0 = 0; x0 < W; x0 += 64) {          // one coalesced 512-byte load per step, the class test of 64 pixels as one ballot
+      const int x = x0 + lane;
+      const unsigned long long bal = __ballot(x < W && m[(long long)y * W + x] == k);
+      cnt += (unsigned)__popcll(bal);
+      if (lane == 0) bits[y * wpr + (x0 >> 5)] = (unsigned)bal;
+      if (lane == 1 && (x0 >> 5) + 1 < wpr) bits[y * wpr + (x0 >> 5) + 1] = (unsigned)(bal >> 32);
+    }
+  return cnt;
+}
+
+// IoU counts of the packed mask with the ellipse (cx, cy, q[0], q[1], q[2] degrees): pixels inside the ellipse (ne) and those of them set in
+// the mask (ni), over the rows y_lo + part * 64 + lane (+ 64 * ROWW ...) of its bounding box, summed over the wave; every lane computes the
+// same parameters.  One evaluation of the search (ellipse_fit_k) and the whole of ellipse_counts_k.
+template <int ROWW>
+__device__ __forceinline__ void evaluate_ell(int H, int W, const float* lxs, const float* lys, const unsigned* bits, int wpr, double cx, double cy,
+                                             int lane, int part, const double* q, unsigned& ne_out, unsigned& ni_out) {
+  double el[5] = {cx, cy, q[0], q[1], q[2] / 180. * PI_REF};
+  double nm[5];
+  normalise(el, H, W, nm);
+  const Ell E = {(float)nm[0], (float)nm[1], (float)nm[2], (float)nm[3], (float)cos(nm[4]), (float)sin(nm[4])};
+  // Only pixels inside the ellipse count (ne, ni), and the ellipse lies within max(a, b) of its centre: rows of the
+  // bounding box (0.1 % + 2 pixels of slack, orders of magnitude above float32 round-off) instead of the frame.
+  // Degenerate parameters (NaN / huge axes) fall back to the full frame, every pixel tested.
+  int y_lo = 0, y_hi = H - 1, x_lo = 0, x_hi = W - 1;
+  const float rr = fmaxf(E.a, E.b) * 1.001f;
+  const bool tame = rr < 4.f && fabsf(E.cx) < 4.f && fabsf(E.cy) < 4.f && fminf(E.a, E.b) > 1e-3f;
+  const float sx = 0.5f * (float)(W - 1), sy = 0.5f * (float)(H - 1);
+  if (tame) {
+    const int xl = (int)floorf((E.cx - rr + 1.f) * sx) - 2, xh = (int)ceilf((E.cx + rr + 1.f) * sx) + 2;
+    const int yl = (int)floorf((E.cy - rr + 1.f) * sy) - 2, yh = (int)ceilf((E.cy + rr + 1.f) * sy) + 2;
+    y_lo = max(yl, 0); y_hi = min(yh, H - 1);
+    x_lo = max(xl, 0); x_hi = min(xh, W - 1);
+  }
+  unsigned ne = 0, ni = 0;
+  if (y_hi >= y_lo && x_hi >= x_lo) {
+    // the row quadratic A dx^2 + Bq dx + C <= 0 (approximate arithmetic: it only seeds the exact walk)
+    const float ia = 1.f / (E.a * E.a), ib = 1.f / (E.b * E.b);
+    const float A = E.ct * E.ct * ia + E.st * E.st * ib, Bc = 2.f * E.st * E.ct * (ia - ib), Cc = E.st * E.st * ia + E.ct * E.ct * ib;
+    for (int y = y_lo + part * 64 + lane; y <= y_hi; y += 64 * ROWW) {
+      const float dy = __fsub_rn(lys[y], E.cy);
+      const float dyst = __fmul_rn(dy, E.st), dyct = __fmul_rn(dy, E.ct);
+      const unsigned* rowbits = bits + y * wpr;
+      // pixels [t0, t1] of the row tested one by one; an interval [il, ir] counted as a whole
+      int t0 = 0, t1 = -1, il = 0, ir = -1;
+      if (!tame) {
+        t0 = x_lo; t1 = x_hi;
+      } else {
+        const float Bq = Bc * dy, C = Cc * dy * dy - 1.f, disc = Bq * Bq - 4.f * A * C;
+        const int xv = (int)floorf((-Bq / (2.f * A) + E.cx + 1.f) * sx);        // pixel next to the row's closest approach
+        bool whole = false;
+        if (!(disc > 0.f)) {
+          // the row misses the ellipse (or grazes it): round-off can only matter next to the closest approach
+          t0 = max(xv - 4, 0); t1 = min(xv + 5, W - 1);
+          whole = t1 >= t0 && (inside_px(E, lxs[t0], dyst, dyct) || inside_px(E, lxs[t1], dyst, dyct));
+        } else {
+          const float sq = sqrtf(disc), dl = (-Bq - sq) / (2.f * A), dr = (-Bq + sq) / (2.f * A);
+          il = (int)ceilf((dl + E.cx + 1.f) * sx);
+          ir = (int)floorf((dr + E.cx + 1.f) * sx);
+          if (ir - il < 12) {
+            // short interval (tangent rows): its pixels and four more on either side, one by one; the outermost must be outside
+            t0 = max(il - 4, 0); t1 = min(ir + 4, W - 1);
+            whole = t1 >= t0 && ((t0 > 0 && inside_px(E, lxs[t0], dyst, dyct)) || (t1 < W - 1 && inside_px(E, lxs[t1], dyst, dyct)));
+            il = 0; ir = -1;
+          } else {
+            // walk each end with the exact predicate: il inside and il - 1 outside (or il = 0), ir inside and ir + 1 outside (or ir = W - 1)
+            il = min(max(il, 0), W - 1); ir = min(max(ir, 0), W - 1);
+            int steps = 0;
+            while (steps < 8 && il > 0 && inside_px(E, lxs[il - 1], dyst, dyct)) { --il; ++steps; }
+            while (steps < 8 && il < W - 1 && !inside_px(E, lxs[il], dyst, dyct)) { ++il; ++steps; }
+            steps = 0;
+            while (steps < 8 && ir < W - 1 && inside_px(E, lxs[ir + 1], dyst, dyct)) { ++ir; ++steps; }
+            while (steps < 8 && ir > 0 && !inside_px(E, lxs[ir], dyst, dyct)) { --ir; ++steps; }
+            const bool settled = il <= ir && inside_px(E, lxs[il], dyst, dyct) && (il == 0 || !inside_px(E, lxs[il - 1], dyst, dyct)) &&
+                                 inside_px(E, lxs[ir], dyst, dyct) && (ir == W - 1 || !inside_px(E, lxs[ir + 1], dyst, dyct));
+            if (!settled) { whole = true; il = 0; ir = -1; }
+          }
+        }
+        if (whole) { t0 = 0; t1 = W - 1; }          // something unexpected: every pixel of the row, as the reference does
+      }
+      for (int x = t0; x <= t1; ++x)
+        if (inside_px(E, lxs[x], dyst, dyct)) { ++ne; ni += (rowbits[x >> 5] >> (x & 31)) & 1u; }
+      if (ir >= il) {
+        ne += (unsigned)(ir - il + 1);
+        ni += row_pop(rowbits, il, ir);
+      }
+    }
+  }
+  for (int o = 32; o >= 1; o >>= 1) { ne += __shfl_xor(ne, o); ni += __shfl_xor(ni, o); }
+  ne_out = ne; ni_out = ni;
+}
+
 // LOCAL: the waves of a search meet through LDS flags of their own instead of the workgroup barrier, so that MANY searches can share a
 // workgroup without running in lock step (eight searches per workgroup: 16 of the chip's 256 compute units host the batch's 128
 // searches instead of 64 -- a compute unit that hosts a search wave cannot take a workgroup of the network's persistent kernels,
@@ -160,15 +257,7 @@ __global__ __launch_bounds__(128 * FIT_PAIRS * ROWW) void ellipse_fit_k(const lo
   }
   const long long* m = mask + (long long)fr * H * W;
   const int k = cls[e];
-  unsigned cnt = 0;            // (wave-uniform: ballots); the waves of the search pack the rows in turn
-  for (int y = wv; y < H; y += NW)
-    for (int x0 = 0; x0 < W; x0 += 64) {          // one coalesced 512-byte load per step, the class test of 64 pixels as one ballot
-      const int x = x0 + lane;
-      const unsigned long long bal = __ballot(x < W && m[(long long)y * W + x] == k);
-      cnt += (unsigned)__popcll(bal);
-      if (lane == 0) bits[y * wpr + (x0 >> 5)] = (unsigned)bal;
-      if (lane == 1 && (x0 >> 5) + 1 < wpr) bits[y * wpr + (x0 >> 5) + 1] = (unsigned)(bal >> 32);
-    }
+  const unsigned cnt = pack_mask_rows(m, k, H, W, bits, wpr, lane, wv, NW);   // the waves of the search pack the rows in turn
   int parity = 0;
   // every wave leaves its two words, all meet at the barrier and read the sums per candidate (double buffered: one barrier per exchange)
   auto exchange = [&](unsigned m0, unsigned m1, unsigned* s0, unsigned* s1) {
@@ -197,81 +286,8 @@ __global__ __launch_bounds__(128 * FIT_PAIRS * ROWW) void ellipse_fit_k(const lo
   const double cx = init[e * 5 + 0], cy = init[e * 5 + 1];
   double now[3] = {init[e * 5 + 2], init[e * 5 + 3], init[e * 5 + 4] * 180. / PI_REF}, d[3] = {1.0, 1.0, 1.0};
 
-  // IoU of the packed mask with the ellipse (cx, cy, q[0], q[1], q[2] degrees); every lane computes the same parameters
   auto evaluate = [&](const double* q, unsigned& ne_out, unsigned& ni_out) {
-    double el[5] = {cx, cy, q[0], q[1], q[2] / 180. * PI_REF};
-    double nm[5];
-    normalise(el, H, W, nm);
-    const Ell E = {(float)nm[0], (float)nm[1], (float)nm[2], (float)nm[3], (float)cos(nm[4]), (float)sin(nm[4])};
-    // Only pixels inside the ellipse count (ne, ni), and the ellipse lies within max(a, b) of its centre: rows of the
-    // bounding box (0.1 % + 2 pixels of slack, orders of magnitude above float32 round-off) instead of the frame.
-    // Degenerate parameters (NaN / huge axes) fall back to the full frame, every pixel tested.
-    int y_lo = 0, y_hi = H - 1, x_lo = 0, x_hi = W - 1;
-    const float rr = fmaxf(E.a, E.b) * 1.001f;
-    const bool tame = rr < 4.f && fabsf(E.cx) < 4.f && fabsf(E.cy) < 4.f && fminf(E.a, E.b) > 1e-3f;
-    const float sx = 0.5f * (float)(W - 1), sy = 0.5f * (float)(H - 1);
-    if (tame) {
-      const int xl = (int)floorf((E.cx - rr + 1.f) * sx) - 2, xh = (int)ceilf((E.cx + rr + 1.f) * sx) + 2;
-      const int yl = (int)floorf((E.cy - rr + 1.f) * sy) - 2, yh = (int)ceilf((E.cy + rr + 1.f) * sy) + 2;
-      y_lo = max(yl, 0); y_hi = min(yh, H - 1);
-      x_lo = max(xl, 0); x_hi = min(xh, W - 1);
-    }
-    unsigned ne = 0, ni = 0;
-    if (y_hi >= y_lo && x_hi >= x_lo) {
-      // the row quadratic A dx^2 + Bq dx + C <= 0 (approximate arithmetic: it only seeds the exact walk)
-      const float ia = 1.f / (E.a * E.a), ib = 1.f / (E.b * E.b);
-      const float A = E.ct * E.ct * ia + E.st * E.st * ib, Bc = 2.f * E.st * E.ct * (ia - ib), Cc = E.st * E.st * ia + E.ct * E.ct * ib;
-      for (int y = y_lo + part * 64 + lane; y <= y_hi; y += 64 * ROWW) {
-        const float dy = __fsub_rn(lys[y], E.cy);
-        const float dyst = __fmul_rn(dy, E.st), dyct = __fmul_rn(dy, E.ct);
-        const unsigned* rowbits = bits + y * wpr;
-        // pixels [t0, t1] of the row tested one by one; an interval [il, ir] counted as a whole
-        int t0 = 0, t1 = -1, il = 0, ir = -1;
-        if (!tame) {
-          t0 = x_lo; t1 = x_hi;
-        } else {
-          const float Bq = Bc * dy, C = Cc * dy * dy - 1.f, disc = Bq * Bq - 4.f * A * C;
-          const int xv = (int)floorf((-Bq / (2.f * A) + E.cx + 1.f) * sx);        // pixel next to the row's closest approach
-          bool whole = false;
-          if (!(disc > 0.f)) {
-            // the row misses the ellipse (or grazes it): round-off can only matter next to the closest approach
-            t0 = max(xv - 4, 0); t1 = min(xv + 5, W - 1);
-            whole = t1 >= t0 && (inside_px(E, lxs[t0], dyst, dyct) || inside_px(E, lxs[t1], dyst, dyct));
-          } else {
-            const float sq = sqrtf(disc), dl = (-Bq - sq) / (2.f * A), dr = (-Bq + sq) / (2.f * A);
-            il = (int)ceilf((dl + E.cx + 1.f) * sx);
-            ir = (int)floorf((dr + E.cx + 1.f) * sx);
-            if (ir - il < 12) {
-              // short interval (tangent rows): its pixels and four more on either side, one by one; the outermost must be outside
-              t0 = max(il - 4, 0); t1 = min(ir + 4, W - 1);
-              whole = t1 >= t0 && ((t0 > 0 && inside_px(E, lxs[t0], dyst, dyct)) || (t1 < W - 1 && inside_px(E, lxs[t1], dyst, dyct)));
-              il = 0; ir = -1;
-            } else {
-              // walk each end with the exact predicate: il inside and il - 1 outside (or il = 0), ir inside and ir + 1 outside (or ir = W - 1)
-              il = min(max(il, 0), W - 1); ir = min(max(ir, 0), W - 1);
-              int steps = 0;
-              while (steps < 8 && il > 0 && inside_px(E, lxs[il - 1], dyst, dyct)) { --il; ++steps; }
-              while (steps < 8 && il < W - 1 && !inside_px(E, lxs[il], dyst, dyct)) { ++il; ++steps; }
-              steps = 0;
-              while (steps < 8 && ir < W - 1 && inside_px(E, lxs[ir + 1], dyst, dyct)) { ++ir; ++steps; }
-              while (steps < 8 && ir > 0 && !inside_px(E, lxs[ir], dyst, dyct)) { --ir; ++steps; }
-              const bool settled = il <= ir && inside_px(E, lxs[il], dyst, dyct) && (il == 0 || !inside_px(E, lxs[il - 1], dyst, dyct)) &&
-                                   inside_px(E, lxs[ir], dyst, dyct) && (ir == W - 1 || !inside_px(E, lxs[ir + 1], dyst, dyct));
-              if (!settled) { whole = true; il = 0; ir = -1; }
-            }
-          }
-          if (whole) { t0 = 0; t1 = W - 1; }          // something unexpected: every pixel of the row, as the reference does
-        }
-        for (int x = t0; x <= t1; ++x)
-          if (inside_px(E, lxs[x], dyst, dyct)) { ++ne; ni += (rowbits[x >> 5] >> (x & 31)) & 1u; }
-        if (ir >= il) {
-          ne += (unsigned)(ir - il + 1);
-          ni += row_pop(rowbits, il, ir);
-        }
-      }
-    }
-    for (int o = 32; o >= 1; o >>= 1) { ne += __shfl_xor(ne, o); ni += __shfl_xor(ni, o); }
-    ne_out = ne; ni_out = ni;
+    evaluate_ell<ROWW>(H, W, lxs, lys, bits, wpr, cx, cy, lane, part, q, ne_out, ni_out);
   };
   auto iou = [&](unsigned ne, unsigned ni) -> float {
     const float fi = (float)ni;
@@ -332,6 +348,41 @@ __global__ __launch_bounds__(128 * FIT_PAIRS * ROWW) void ellipse_fit_k(const lo
     out[e * 5 + 0] = cx; out[e * 5 + 1] = cy; out[e * 5 + 2] = now[0]; out[e * 5 + 3] = now[1];
     out[e * 5 + 4] = now[2] / 180.0 * PI_REF;
     if (evals) evals[e] = nev;
+  }
+}
+
+// One evaluation per ellipse through the functions the search calls: a workgroup of ROWW waves per ellipse, wave = part.  counts[e] = (pixels
+// of class cls[e] in frame frame_of[e], pixels inside the ellipse, pixels in both); ell[e] = (cx, cy, a, b) pixels, angle in degrees.
+template <int ROWW>
+__global__ __launch_bounds__(64 * ROWW) void ellipse_counts_k(const long long* __restrict__ mask, int nframes, const int* __restrict__ frame_of,
+                                                              const int* __restrict__ cls, int H, int W, const float* __restrict__ xs,
+                                                              const float* __restrict__ ys, const double* __restrict__ ell,
+                                                              unsigned* __restrict__ counts) {
+  extern __shared__ unsigned fit_lds[];  // xs[W], ys[H], [ROWW waves][nseg, ne, ni], [H][wpr] packed mask
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int wpr = (W + 31) >> 5;
+  float* lxs = (float*)fit_lds;
+  float* lys = lxs + W;
+  unsigned* sums = fit_lds + W + H;
+  unsigned* bits = sums + 3 * ROWW;
+  for (int i = threadIdx.x; i < W; i += blockDim.x) lxs[i] = xs[i];
+  for (int i = threadIdx.x; i < H; i += blockDim.x) lys[i] = ys[i];
+  const int e = blockIdx.x;
+  const int fr = frame_of[e];
+  if (fr < 0 || fr >= nframes) {   // a frame the mask tensor does not hold: all ones, read nothing (the whole workgroup leaves)
+    if (threadIdx.x < 3) counts[e * 3 + threadIdx.x] = 0xffffffffu;
+    return;
+  }
+  const unsigned cnt = pack_mask_rows(mask + (long long)fr * H * W, cls[e], H, W, bits, wpr, lane, wave, ROWW);
+  __syncthreads();
+  unsigned ne, ni;
+  evaluate_ell<ROWW>(H, W, lxs, lys, bits, wpr, ell[e * 5 + 0], ell[e * 5 + 1], lane, wave, ell + e * 5 + 2, ne, ni);
+  if (lane == 0) { sums[wave * 3] = cnt; sums[wave * 3 + 1] = ne; sums[wave * 3 + 2] = ni; }
+  __syncthreads();
+  if (threadIdx.x < 3) {
+    unsigned t = 0;
+    for (int w = 0; w < ROWW; ++w) t += sums[w * 3 + threadIdx.x];
+    counts[e * 3 + threadIdx.x] = t;
   }
 }
 
@@ -404,4 +455,21 @@ extern "C" int egne_ellipse_fit(const int64_t* mask, int nframes, const int32_t*
     hipLaunchKernelGGL((ellipse_fit_k<1, 4>), dim3((unsigned)n), dim3(512), lds, st, mk, nframes, frame_of, cls, n, H, W, xs, ys, init, out, evals);
   }
   return egne::check_launch("egne_ellipse_fit");
+}
+
+extern "C" int egne_ellipse_iou_counts(const int64_t* mask, int nframes, const int32_t* frame_of, const int32_t* cls, int n, int H, int W,
+                                       const float* xs, const float* ys, const double* ell, uint32_t* counts, int roww, void* stream) {
+  EGNE_REQUIRE(mask && frame_of && cls && xs && ys && ell && counts, "ellipse_iou_counts: null pointer");
+  EGNE_REQUIRE(n > 0 && nframes > 0 && H > 1 && W > 1, "ellipse_iou_counts: bad shape");
+  EGNE_REQUIRE(roww == 1 || roww == 4, "ellipse_iou_counts: roww must be 1 or 4, got %d", roww);
+  const size_t per_search = ((size_t)H * ((W + 31) / 32) + 32) * 4, fixed = (size_t)(W + H) * 4;
+  EGNE_REQUIRE(2 * per_search + fixed <= 64 * 1024, "ellipse_iou_counts: %dx%d masks do not fit LDS", H, W);
+  hipStream_t st = (hipStream_t)stream;
+  const long long* mk = (const long long*)mask;
+  const size_t lds = fixed + per_search;            // (per_search leaves 32 words for the 3 * roww partial sums)
+  if (roww == 4)
+    hipLaunchKernelGGL((ellipse_counts_k<4>), dim3((unsigned)n), dim3(256), lds, st, mk, nframes, frame_of, cls, H, W, xs, ys, ell, counts);
+  else
+    hipLaunchKernelGGL((ellipse_counts_k<1>), dim3((unsigned)n), dim3(64), lds, st, mk, nframes, frame_of, cls, H, W, xs, ys, ell, counts);
+  return egne::check_launch("egne_ellipse_iou_counts");
 }

@@ -221,6 +221,29 @@ def fit_ellipses(mask, frame_of, cls, init, return_evals=False):
     return (out.cpu().numpy(), ev.cpu().numpy()) if return_evals else out.cpu().numpy()
 
 
+def ellipse_iou_counts(mask, frame_of, cls, ell, roww=1):
+    """One evaluation of the search per ellipse, through the device functions the search kernel calls (csrc/fit.hip): the three
+    counts of calc_ell_iou (utils.py:176-204) before the division.
+
+    mask [F,H,W] int64 class maps on the GPU; frame_of / cls [n]; ell [n,5] (cx, cy, a, b) pixels and the angle in DEGREES (what one
+    evaluation of the search is handed); roww 1 or 4 = waves that share the rows.  Returns uint32 [n,3] (nseg, nell, inter); a
+    frame_of outside [0, F) gives 0xffffffff three times."""
+    require_cuda(mask, "mask")
+    L = _lib.lib()
+    dev = mask.device
+    F, H, W = mask.shape
+    n = len(frame_of)
+    fo = torch.as_tensor(np.asarray(frame_of, dtype=np.int32)).to(dev)
+    cl = torch.as_tensor(np.asarray(cls, dtype=np.int32)).to(dev)
+    el = torch.as_tensor(np.asarray(ell, dtype=np.float64).reshape(n, 5)).to(dev)
+    out = torch.empty((n, 3), dtype=torch.int32, device=dev)
+    xs, ys = _mesh_axes(H, W, dev)
+    m = mask.contiguous()
+    _lib.check(L.egne_ellipse_iou_counts(m.data_ptr(), F, fo.data_ptr(), cl.data_ptr(), n, H, W, xs.data_ptr(), ys.data_ptr(),
+                                         el.data_ptr(), out.data_ptr(), int(roww), _lib.stream_ptr()), "ellipse_iou_counts")
+    return out.cpu().numpy().view(np.uint32)
+
+
 def ellipse_seeds_from_pred(elPred, H, W):
     """evaluate.py:135-151 on the device: elPred [F,10] float32 (normalised ellipses of the regression head)
     -> (init [2F,5] float64 pixel ellipses, frame_of [2F] int32, cls [2F] int32), all on the GPU.

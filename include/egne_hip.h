@@ -668,12 +668,24 @@ int egne_pack_conv_weight_dgrad(const float* w_oihw, int Cout, int Cin, int kh, 
  * ellipses -> init [2*nframes][5] float64 pixel ellipses via my_ellipse(p).transform(H)
  * (helperfunctions.py:124-129), fit 2f = iris / class 1 from elPred[f][0:5], fit 2f+1 = pupil / class 2 from
  * elPred[f][5:10]; also fills frame_of / cls [2*nframes].
+ *
+ * egne_ellipse_iou_counts: ONE evaluation of that search per ellipse, through the same device functions the search
+ * kernel calls (mask packing and the row-interval evaluation), for tests that compare every count with the
+ * reference instead of the search's final result only.  ell [n][5] = (cx, cy, a, b) in pixels and the angle in
+ * DEGREES -- what one evaluation of the search is handed; counts [n][3] = pixels of class cls[i] in frame
+ * frame_of[i], pixels inside the ellipse, pixels in both (utils.py:176-204 before the division).  roww = 1: one
+ * wave, 64 rows per pass; roww = 4: four waves, 256 rows per pass, partial sums added across the waves (the two
+ * row splits of the search's launch forms).  A frame_of outside [0, nframes) writes 0xffffffff three times and
+ * reads nothing.
  */
 int egne_ellipse_fit(const int64_t* mask, int nframes, const int32_t* frame_of, const int32_t* cls, int n,
                      int H, int W, const float* xs, const float* ys, const double* init, double* out,
                      int32_t* evals, void* stream);
 int egne_ellipse_init_from_pred(const float* elPred, int nframes, int H, int W, double* init,
                                 int32_t* frame_of, int32_t* cls, void* stream);
+int egne_ellipse_iou_counts(const int64_t* mask, int nframes, const int32_t* frame_of, const int32_t* cls, int n,
+                            int H, int W, const float* xs, const float* ys, const double* ell, uint32_t* counts,
+                            int roww, void* stream);
 
 /* Device-side batch preparation (the reference does this per sample on the host in its Dataset).
  * egne_dist_maps: out[b][c] = helperfunctions.one_hot2dist(label[b] == c) (helperfunctions.py:356-371, called from

@@ -66,10 +66,10 @@ def mesh_f32(H, W):
     return np.broadcast_to(xs[None, :], (H, W)), np.broadcast_to(ys[:, None], (H, W))
 
 
-def ell_iou(seg, el_px_deg, mesh):
-    """utils.py:176-204 calc_ell_iou(seg, el, mesh, nor=False, angle_nor=True).
-    seg: bool [H,W]; el_px_deg: (cx, cy, a, b, angle in degrees) in pixels."""
-    Hh, Ww = seg.shape
+def ell_inside(shape, el_px_deg, mesh):
+    """The rasterised ellipse of utils.py:176-204 calc_ell_iou(seg, el, mesh, nor=False, angle_nor=True): bool [H,W].
+    shape = (H, W); el_px_deg: (cx, cy, a, b, angle in degrees) in pixels."""
+    Hh, Ww = shape
     el = np.array(el_px_deg, dtype=np.float64)
     el[4] = el[4] / 180. * PI_REF
     Hm = np.array([[2 / Ww, 0, -1], [0, 2 / Hh, -1], [0, 0, 1]])
@@ -83,12 +83,30 @@ def ell_iou(seg, el_px_deg, mesh):
     Y = (-dx) * st + dy * ct
     u, v = X / a, Y / b
     wt = u * u + v * v - f(1)
-    ell = wt <= 0
+    return wt <= 0
+
+
+def ell_counts(seg, el_px_deg, mesh):
+    """The three pixel counts of calc_ell_iou: (nseg, nell, inter) = pixels of the mask, pixels inside the
+    ellipse, pixels in both.  seg: bool [H,W]; el_px_deg as for ell_inside."""
+    ell = ell_inside(seg.shape, el_px_deg, mesh)
     inter = int(np.count_nonzero(ell & seg))
     nseg = int(np.count_nonzero(seg))
     nell = int(np.count_nonzero(ell))
+    return nseg, nell, inter
+
+
+def score_of_counts(nseg, nell, inter):
+    """The float32 score expression of calc_ell_iou on its three counts (integer counts are exact in float32)."""
+    f = np.float32
     with np.errstate(invalid="ignore", divide="ignore"):
         return float(f(inter) / f(f(f(nseg) + f(nell)) - f(inter)))
+
+
+def ell_iou(seg, el_px_deg, mesh):
+    """utils.py:176-204 calc_ell_iou(seg, el, mesh, nor=False, angle_nor=True).
+    seg: bool [H,W]; el_px_deg: (cx, cy, a, b, angle in degrees) in pixels."""
+    return score_of_counts(*ell_counts(seg, el_px_deg, mesh))
 
 
 def fit_ellipse(seg, ell_para, max_sweeps=40, count_evals=False):
