@@ -213,7 +213,7 @@ __global__ __launch_bounds__(256) void conv1x1_f16x3_kernel(const egne_conv_desc
 // average over the 2x2 window of leaky(x * scale + shift) -- 8 loads of 16 bytes per 16-channel group instead of 2, no pooled
 // tensor in HBM (it was written by norm_act_pool2_k and read back by the streaming kernel: one launch and 2 x the pooled bytes
 // less).  Same weights and K order as conv1x1_f16x3_kernel; p.H / p.W are the INPUT size, p.Ho / p.Wo = H/2, W/2.
-template <int TN>
+template <int TN, bool STATS = false>
 __global__ __launch_bounds__(256) void conv1x1_pool_f16x3_kernel(const egne_conv_desc p, const _Float16* __restrict__ fhi,
                                                                  const _Float16* __restrict__ flo, float a_scale, float out_scale,
                                                                  int G, long long M, int nblocks) {
@@ -230,7 +230,9 @@ __global__ __launch_bounds__(256) void conv1x1_pool_f16x3_kernel(const egne_conv
   __syncthreads();
 
   const float slope = p.act == EGNE_ACT_RELU ? 0.f : (p.act == EGNE_ACT_LEAKY ? 0.01f : 1.f);
-  f32x4 bias[TN][4];
+  // (STATS: the bias is fetched per block in the epilogue -- 16 TN registers that would cost the TN = 2 shape its third wave per SIMD)
+  [[maybe_unused]] f32x4 bias[STATS ? 1 : TN][4];
+  if constexpr (!STATS) {
 #pragma unroll
   for (int tn = 0; tn < TN; ++tn)
 #pragma unroll
@@ -238,15 +240,39 @@ __global__ __launch_bounds__(256) void conv1x1_pool_f16x3_kernel(const egne_conv
       const int n = (nt0 + tn) * 32 + 8 * j + 4 * kq;
       bias[tn][j] = (p.bias && n < p.Cout_store) ? *(const f32x4*)(p.bias + n) : (f32x4)(0.f);
     }
+  }
   const int H = p.H, W = p.W, Hp = p.Ho, Wp = p.Wo, hwp = Hp * Wp;
   const float s4 = 0.25f * a_scale;
 
-  for (int blk = blockIdx.x * 4 + wave; blk < nblocks; blk += gridDim.x * 4) {
-    const long long m0 = (long long)blk * 32;
-    const long long rows = M - m0 < 32 ? M - m0 : 32;
+  // p.stats_ws: per (frame, chunk, channel) fp64 sum / sum of squares of the stored values, finished by egne_norm_stats_finish (the
+  // InstanceNorm statistics of the next dense block's input: no pass over this launch's output).  The work is then split per FRAME:
+  // a unit is a run of cb 32-pixel blocks of one frame (the frame's last block may be partial) and one chunk of the workspace, walked
+  // by one wave whose running sums never leave the frame; fixed chunks, fixed order of summation: the same bits every run.  Without
+  // statistics a unit is one 32-pixel block of the flat pixel list, as before.
+  constexpr bool stats = STATS;
+  const int bpf = (hwp + 31) >> 5, cb = stats ? (bpf + p.stats_nchunk - 1) / p.stats_nchunk : 1;
+  // (stats) per wave behind the weights: a patch of 32 pixels x 32 channels (fp32, pixel pitch 36 floats: the 16-byte writes of a
+  // quarter wave and the transposed reads both spread over the banks)
+  constexpr int PP = 36;
+  [[maybe_unused]] float* const patch = (float*)(wl + (long long)G * TN * 2 * 64 * 8) + wave * (32 * PP);
+  [[maybe_unused]] const int rd = (lane >> 5) * PP + (lane & 31);        // reader: channel lane & 31 of pixels 2 i + (lane >> 5)
+
+  for (int unit = blockIdx.x * 4 + wave; unit < nblocks; unit += gridDim.x * 4) {
+   long long mfirst = (long long)unit * 32, mend = M;
+   if (stats) {
+     const int fb = unit / p.stats_nchunk, ck = unit - fb * p.stats_nchunk;
+     mfirst = (long long)fb * hwp + (long long)ck * cb * 32;
+     mend = (long long)(fb + 1) * hwp;
+   }
+   if (mend > mfirst + (long long)cb * 32) mend = mfirst + (long long)cb * 32;
+   [[maybe_unused]] double ssum[TN], qsum[TN];        // (stats) running sums of channel 32 tn + (lane & 31) over this lane's half of the pixels
+#pragma unroll
+   for (int tn = 0; tn < TN; ++tn) ssum[tn] = qsum[tn] = 0.;
+   for (long long m0 = mfirst; m0 < mend; m0 += 32) {
+    const long long rows = mend - m0 < 32 ? mend - m0 : 32;
     const int b0 = (int)(m0 / hwp);                       // frame of the block's first pixel; a block spans at most two frames
     const long long m = m0 + li;
-    const bool valid = m < M;
+    const bool valid = li < rows;
     const int b = valid ? (int)(m / hwp) : b0;
     const int r = (int)(m - (long long)b * hwp);
     const int yp = valid ? r / Wp : 0, xp = valid ? r - yp * Wp : 0;
@@ -307,17 +333,44 @@ __global__ __launch_bounds__(256) void conv1x1_pool_f16x3_kernel(const egne_conv
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
         const int n = (nt0 + tn) * 32 + 8 * j + 4 * kq;
-        f32x4 v;
+        f32x4 v, bv;
+        if constexpr (STATS) bv = (p.bias && n < p.Cout_store) ? *(const f32x4*)(p.bias + n) : (f32x4)(0.f);
+        else bv = bias[tn][j];
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
-          const float t = acc[tn][4 * j + e] * out_scale + bias[tn][j][e];
+          const float t = acc[tn][4 * j + e] * out_scale + bv[e];
           v[e] = fmaxf(t, t * slope);
         }
         if (tn == 0 && j == 0) bad |= egne_nonfinite(v[0]);       // lane = pixel: one channel per pixel (common.h)
         const int off = n < p.Cout_store ? (li * (int)p.out_pix_stride + p.out_ch_off + n) * 4 : (int)OOB;
         __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), ro, off, 0, 0);
+        if constexpr (stats) {
+          // lane = pixel holds 4 channels; the sums run over pixels: the 32 channels of a block through the wave's LDS patch, read
+          // back transposed (lane = channel, 16 pixels each), accumulated in fp64 in a fixed order
+          *(f32x4*)&patch[li * PP + 8 * j + 4 * kq] = valid ? v : (f32x4)(0.f);
+          if (j == 3) {
+            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");      // one wave: its own LDS writes are visible to its own reads
+            double s_ = ssum[tn], q_ = qsum[tn];
+#pragma unroll
+            for (int i = 0; i < 16; ++i) {
+              const double x = (double)patch[i * 2 * PP + rd];
+              s_ += x; q_ += x * x;
+            }
+            ssum[tn] = s_; qsum[tn] = q_;
+          }
+        }
       }
     egne_ovf_commit(bad, p.ovf_flag);
+   }
+   if constexpr (stats) {
+#pragma unroll
+     for (int tn = 0; tn < TN; ++tn) {
+       const double s_ = ssum[tn] + __shfl_xor(ssum[tn], 32), q_ = qsum[tn] + __shfl_xor(qsum[tn], 32);
+       const int n = (nt0 + tn) * 32 + lane;
+       if (lane < 32 && n < p.Cout_store)      // (unit = frame * stats_nchunk + chunk: the workspace's own order)
+         ((double2*)p.stats_ws)[(long long)unit * p.Cout_store + n] = make_double2(s_, q_);
+     }
+   }
   }
 }
 
@@ -450,22 +503,40 @@ extern "C" int egne_conv1x1_pool2_f16x3_fwd(const egne_conv_desc* dp, const void
   const long long nb = (M + 31) / 32;
   EGNE_REQUIRE(nb < (1ll << 31), "conv1x1_pool2_f16: too many pixels");
   const int TN = d.CoutP / 32;        // all output channels in one workgroup: the (4x larger) input is read once
-  const size_t lds = (size_t)G * TN * 2 * 64 * 8 * sizeof(_Float16);
+  // statistics of the stored output (d.stats_ws, [B][stats_nchunk][Cout_store][2] fp64): a chunk = ceil(blocks per frame / stats_nchunk)
+  // consecutive 32-pixel blocks of one frame, every chunk non-empty; + one 32 x 36 fp32 patch per wave behind the weights
+  const int bpf = (d.Ho * d.Wo + 31) / 32;
+  EGNE_REQUIRE(!d.stats_ws || (((uintptr_t)d.stats_ws & 15) == 0 && d.stats_nchunk >= 1 && d.stats_nchunk <= bpf &&
+                               (long long)(d.stats_nchunk - 1) * ((bpf + d.stats_nchunk - 1) / d.stats_nchunk) < bpf &&
+                               (long long)d.B * d.stats_nchunk < (1ll << 31)),
+               "conv1x1_pool2_f16: stats_ws needs 1 <= stats_nchunk <= %d blocks per frame, no empty chunk", bpf);
+  const size_t lds = (size_t)G * TN * 2 * 64 * 8 * sizeof(_Float16) + (d.stats_ws ? (size_t)4 * 32 * 36 * sizeof(float) : 0);
   EGNE_REQUIRE(lds <= 80 * 1024, "conv1x1_pool2_f16: K = %d groups of 16 does not fit the LDS weight image", G);
   static bool once = [] {
     return hipFuncSetAttribute((const void*)conv1x1_pool_f16x3_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024) == hipSuccess &&
            hipFuncSetAttribute((const void*)conv1x1_pool_f16x3_kernel<2>, hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024) == hipSuccess &&
-           hipFuncSetAttribute((const void*)conv1x1_pool_f16x3_kernel<3>, hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024) == hipSuccess;
+           hipFuncSetAttribute((const void*)conv1x1_pool_f16x3_kernel<3>, hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024) == hipSuccess &&
+           hipFuncSetAttribute((const void*)conv1x1_pool_f16x3_kernel<1, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024) == hipSuccess &&
+           hipFuncSetAttribute((const void*)conv1x1_pool_f16x3_kernel<2, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024) == hipSuccess &&
+           hipFuncSetAttribute((const void*)conv1x1_pool_f16x3_kernel<3, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024) == hipSuccess;
   }();
   if (!once) return egne::fail(EGNE_ERR_LAUNCH, "conv1x1_pool2_f16: cannot raise the dynamic LDS limit");
   const int ny = 1;
-  long long gx = (nb + 3) / 4;
+  const long long nu = d.stats_ws ? (long long)d.B * d.stats_nchunk : nb;       // units of work: one per wave and turn (see the kernel)
+  long long gx = (nu + 3) / 4;
   const long long cap = 256 * 8;
   if (gx > cap) gx = cap;
   const float os = 1.0f / (a_scale * w_scale);
   hipStream_t st = (hipStream_t)stream;
-  if (TN == 1) hipLaunchKernelGGL((conv1x1_pool_f16x3_kernel<1>), dim3((unsigned)gx, (unsigned)ny), dim3(256), lds, st, d, (const _Float16*)fhi, (const _Float16*)flo, a_scale, os, G, M, (int)nb);
-  else if (TN == 2) hipLaunchKernelGGL((conv1x1_pool_f16x3_kernel<2>), dim3((unsigned)gx, (unsigned)ny), dim3(256), lds, st, d, (const _Float16*)fhi, (const _Float16*)flo, a_scale, os, G, M, (int)nb);
-  else hipLaunchKernelGGL((conv1x1_pool_f16x3_kernel<3>), dim3((unsigned)gx, (unsigned)ny), dim3(256), lds, st, d, (const _Float16*)fhi, (const _Float16*)flo, a_scale, os, G, M, (int)nb);
+  const dim3 grid((unsigned)gx, (unsigned)ny);
+  const _Float16* h = (const _Float16*)fhi;
+  const _Float16* l = (const _Float16*)flo;
+  if (d.stats_ws) {
+    if (TN == 1) hipLaunchKernelGGL((conv1x1_pool_f16x3_kernel<1, true>), grid, dim3(256), lds, st, d, h, l, a_scale, os, G, M, (int)nu);
+    else if (TN == 2) hipLaunchKernelGGL((conv1x1_pool_f16x3_kernel<2, true>), grid, dim3(256), lds, st, d, h, l, a_scale, os, G, M, (int)nu);
+    else hipLaunchKernelGGL((conv1x1_pool_f16x3_kernel<3, true>), grid, dim3(256), lds, st, d, h, l, a_scale, os, G, M, (int)nu);
+  } else if (TN == 1) hipLaunchKernelGGL((conv1x1_pool_f16x3_kernel<1>), grid, dim3(256), lds, st, d, h, l, a_scale, os, G, M, (int)nu);
+  else if (TN == 2) hipLaunchKernelGGL((conv1x1_pool_f16x3_kernel<2>), grid, dim3(256), lds, st, d, h, l, a_scale, os, G, M, (int)nu);
+  else hipLaunchKernelGGL((conv1x1_pool_f16x3_kernel<3>), grid, dim3(256), lds, st, d, h, l, a_scale, os, G, M, (int)nu);
   return egne::check_launch("egne_conv1x1_pool2_f16x3_fwd");
 }

@@ -67,6 +67,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_halo_f16_kernel(const egne_con
   constexpr int nitems = npx * 8;
   constexpr int NI = (nitems + 255) / 256;
   static_assert(HWd >= 32, "one wrap per 32-pixel step");
+  static_assert(WN < 3 || (NP == 3 && !PS && !POOL && !LAT && NW == 1), "96-wide tile: three products, fp32 slices, no pooled output");
   extern __shared__ __attribute__((aligned(16))) _Float16 ldsh[];
   _Float16* Ahi = ldsh;
   _Float16* Alo = ldsh + npx * LDH;
@@ -79,14 +80,23 @@ __global__ __launch_bounds__(256, 2) void conv3x3_halo_f16_kernel(const egne_con
   const egne_seg sg = p.seg[0];
   const int Cp = sg.Cp;
   const int c4 = tid & 7;
+  // LEAN: the thread index rebuilt where it is needed (lane count of the wave + the wave's number in a scalar register) instead of
+  // one more vector register held through the MFMA loop
+  const int wave_s = __builtin_amdgcn_readfirstlane(wave);
+  auto fresh_tid = [&]() {
+    int l;
+    asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(l));
+    return wave_s * 64 + l;
+  };
   const int S = LAT ? p.dil[0] : 1;          // lattice step
   const unsigned frame_in = (unsigned)p.H * p.W * (unsigned)sg.pix_stride * 4u;
   const unsigned frame_out = (unsigned)p.H * p.W * (unsigned)p.out_pix_stride * 4u;
   const unsigned frame_res = (unsigned)p.H * p.W * (unsigned)p.res_pix_stride * 4u;
 
   // tile-independent per-item constants: halo coordinates (in image pixels, lattice step applied) and byte offset
-  int hyx[NI], roff[NI];
-  {
+  constexpr bool LEAN = WN >= 3;       // 96-wide tile: 96 accumulators -- per-item constants are recomputed per tile, the weight ring's two slots are refilled in place (no copies)
+  int hyx[LEAN ? 1 : NI], roff[LEAN ? 1 : NI];
+  if constexpr (!LEAN) {
     int px = tid >> 3;
     int hy = px / HWd, hx = px - hy * HWd;
 #pragma unroll
@@ -117,10 +127,24 @@ __global__ __launch_bounds__(256, 2) void conv3x3_halo_f16_kernel(const egne_con
   auto map_tile = [&](const Tile& tl) {
     const int ybase = tl.py + S * (tl.y0 - d), xbase = tl.px + S * (tl.x0 - d);
     const int tbase = ((ybase * rstep + xbase * cstep) * (int)sg.pix_stride + sg.ch_off) * 4;
+    if constexpr (LEAN) {
+      const int tf = fresh_tid();       // per tile on purpose: hoisted out of the tile loop these values are 2 * NI registers held through it
+      const int px = tf >> 3, c4f = tf & 7;
+      int hy = px / HWd, hx = px - hy * HWd;
+#pragma unroll
+      for (int i = 0; i < NI; ++i) {
+        const unsigned iy = (unsigned)(ybase + S * hy), ix = (unsigned)(xbase + S * hx);
+        const bool in = tf + 256 * i < nitems && iy < (unsigned)vH && ix < (unsigned)vW;
+        goff[i] = in ? (unsigned)(tbase + (S * hy * rstep + S * hx * cstep) * (int)sg.pix_stride * 4 + c4f * 16) : OOB;
+        hx += 32;
+        if (hx >= HWd) { hx -= HWd; ++hy; }
+      }
+    } else {
 #pragma unroll
     for (int i = 0; i < NI; ++i) {
       const unsigned iy = (unsigned)(ybase + (hyx[i] >> 16)), ix = (unsigned)(xbase + (hyx[i] & 0xffff));
       goff[i] = (iy < (unsigned)vH && ix < (unsigned)vW) ? (unsigned)(tbase + roff[i]) : OOB;
+    }
     }
     rin = make_rsrc(sg.ptr + (long long)tl.b * p.H * p.W * sg.pix_stride, frame_in);
     stage_b = tl.b;
@@ -129,13 +153,20 @@ __global__ __launch_bounds__(256, 2) void conv3x3_halo_f16_kernel(const egne_con
   u32x4 st[NI];
   f32x4 st_sc = {1.f, 1.f, 1.f, 1.f}, st_sh = {0.f, 0.f, 0.f, 0.f};
   unsigned st_cmask = 0;
+  int st_c0 = 0;
+  // scale / shift of the staged chunk's channels (fused InstanceNorm affine).  LEAN: fetched behind the MFMA loop, in front of the
+  // barrier that releases the LDS image -- not eight more registers held through the loop
+  auto load_affine = [&]() {
+    const int cq = (LEAN ? fresh_tid() & 7 : c4) * 4;
+    const bool cok = st_c0 + cq < Cp;
+    st_sc = *(const f32x4*)(cok ? sg.scale + (long long)stage_b * Cp + st_c0 + cq : egne_zero_page);
+    st_sh = *(const f32x4*)(cok ? sg.shift + (long long)stage_b * Cp + st_c0 + cq : egne_zero_page);
+  };
   auto load_chunk = [&](int c0) {
-    const bool cok = PS || c0 + c4 * 4 < Cp;       // (PS: whole 32-channel blocks)
+    const bool cok = PS || c0 + (LEAN ? fresh_tid() & 7 : c4) * 4 < Cp;       // (PS: whole 32-channel blocks)
     st_cmask = cok ? 0u : OOB;
-    if (sg.scale) {
-      st_sc = *(const f32x4*)(cok ? sg.scale + (long long)stage_b * Cp + c0 + c4 * 4 : egne_zero_page);
-      st_sh = *(const f32x4*)(cok ? sg.shift + (long long)stage_b * Cp + c0 + c4 * 4 : egne_zero_page);
-    }
+    st_c0 = c0;
+    if (!LEAN && sg.scale) load_affine();
 #pragma unroll
     for (int i = 0; i < NI; ++i) st[i] = __builtin_amdgcn_raw_buffer_load_b128(rin, (int)(goff[i] | st_cmask), c0 * 4, 0);
   };
@@ -153,12 +184,14 @@ __global__ __launch_bounds__(256, 2) void conv3x3_halo_f16_kernel(const egne_con
         st[i] = __builtin_bit_cast(u32x4, v);
       }
     }
+    const int tid_s = LEAN ? fresh_tid() : tid;
+    const int lofs_s = LEAN ? (tid_s >> 3) * LDH + (tid_s & 7) * 4 : lofs0;
 #pragma unroll
     for (int i = 0; i < NI; ++i) {
-      if (i < NI - 1 || tid + 256 * i < nitems) {
+      if (i < NI - 1 || tid_s + 256 * i < nitems) {
         const f32x4 v = __builtin_bit_cast(f32x4, st[i]);
         // x*a_scale = hi + lo, two elements per (packed) instruction
-        const int o = lofs0 + i * 32 * LDH;
+        const int o = lofs_s + i * 32 * LDH;
         if constexpr (PS) {       // eight stored halves of one plane, as they are
           *(u32x4*)&(c4 >> 2 ? Alo : Ahi)[(tid >> 3) * LDH + (c4 & 3) * 8 + i * 32 * LDH] = st[i];
           continue;
@@ -210,6 +243,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_halo_f16_kernel(const egne_con
   int c0 = 0;
   const int abase = (wrow * WM * HWd + li) * LDH + lh * 8;
   while (true) {
+    if (LEAN && sg.scale) load_affine();
     __syncthreads();
     store_chunk();
     __syncthreads();
@@ -243,7 +277,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_halo_f16_kernel(const egne_con
         qh[s][tn] = __builtin_amdgcn_raw_buffer_load_b128(rwh, wl, o, 0);
         if constexpr (NP == 3) ql[s][tn] = __builtin_amdgcn_raw_buffer_load_b128(rwl, wl, o, 0);
       }
-    constexpr int TAP_UNROLL = NW == 2 ? 1 : 9;   // the NW = 2 shape only fits 2 waves per SIMD with the tap loop rolled
+    constexpr int TAP_UNROLL = (NW == 2 || LEAN) ? 1 : 9;   // the NW = 2 shape only fits 2 waves per SIMD with the tap loop rolled
 #pragma unroll TAP_UNROLL
     for (int tap = 0; tap < 9; ++tap) {
       const int ky = tap / 3, kx = tap - ky * 3;
@@ -259,6 +293,25 @@ __global__ __launch_bounds__(256, 2) void conv3x3_halo_f16_kernel(const egne_con
         for (int tm = 0; tm < WM; ++tm) {
           ah[tm] = *(const h8*)&Ahi[aoff + tm * HWd * LDH + ks * 16];
           if constexpr (NP == 3) al[tm] = *(const h8*)&Alo[aoff + tm * HWd * LDH + ks * 16];
+        }
+        if constexpr (LEAN) {
+          // no copies of the slot: a fragment's registers are refilled (same k-step of the next tap) right behind the MFMAs that read them
+#pragma unroll
+          for (int tn = 0; tn < WN; ++tn) {
+            const h8 wh = __builtin_bit_cast(h8, qh[slot][tn]), wl_ = __builtin_bit_cast(h8, ql[slot][tn]);
+#pragma unroll
+            for (int tm = 0; tm < WM; ++tm) {
+              acc[tm][tn] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al[tm], wh, acc[tm][tn], 0, 0, 0);
+              acc[tm][tn] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[tm], wl_, acc[tm][tn], 0, 0, 0);
+              acc[tm][tn] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[tm], wh, acc[tm][tn], 0, 0, 0);
+            }
+            if (tap + RT < 9) {
+              const int o = wchunk + wtap(tap + RT) * stride_tap + ks * stride_k16 + tn * 1024;
+              qh[slot][tn] = __builtin_amdgcn_raw_buffer_load_b128(rwh, wlane, o, 0);
+              ql[slot][tn] = __builtin_amdgcn_raw_buffer_load_b128(rwl, wlane, o, 0);
+            }
+          }
+          continue;
         }
 #pragma unroll
         for (int tn = 0; tn < WN; ++tn) {
@@ -289,14 +342,19 @@ __global__ __launch_bounds__(256, 2) void conv3x3_halo_f16_kernel(const egne_con
 
     // ---- epilogue: lane holds channel n of 16 pixels x = x_lane + S*c_r, c_r = (r&3) + 8*(r>>2), of tile row tm ----
     {
+      int li_e = li, lh_e = lh, wrow_e = wrow;
+      if constexpr (LEAN) {       // re-derived here: values that only the epilogue reads are not held through the MFMA loop
+        const int te = fresh_tid();
+        li_e = te & 31; lh_e = (te >> 5) & 1; wrow_e = te >> 6;
+      }
       const __amdgpu_buffer_rsrc_t rout = make_rsrc(p.out + (long long)cur.b * p.H * p.W * p.out_pix_stride, frame_out);
       const __amdgpu_buffer_rsrc_t rres =
           make_rsrc(p.residual ? p.residual + (long long)cur.b * p.H * p.W * p.res_pix_stride : nullptr, p.residual ? frame_res : 0u);
-      const int xl = cur.px + S * (cur.x0 + 4 * lh);
+      const int xl = cur.px + S * (cur.x0 + 4 * lh_e);
       const int cmax = xl < vW ? (vW - xl + S - 1) / S : 0;      // c_r < cmax  <=>  x < W
 #pragma unroll
       for (int tn = 0; tn < WN; ++tn) {
-        const int n = (nt0 + tn) * 32 + li;
+        const int n = (nt0 + tn) * 32 + li_e;
         const bool nok = n < p.Cout_store;
         const float bv = (p.bias && nok) ? p.bias[n] : 0.f;
         float ps = 1.f, pt = 0.f;
@@ -305,10 +363,31 @@ __global__ __launch_bounds__(256, 2) void conv3x3_halo_f16_kernel(const egne_con
         [[maybe_unused]] float pool_keep[16];   // (POOL) stored values of the wave's first row, -inf where nothing was stored
 #pragma unroll
         for (int tm = 0; tm < WM; ++tm) {
-          const int y = cur.py + S * (cur.y0 + wrow * WM + tm);
+          const int y = cur.py + S * (cur.y0 + wrow_e * WM + tm);
           const int cm = (nok && y < vH) ? cmax : 0;
           const int pix = y * rstep + xl * cstep;
           const unsigned o0 = (unsigned)((pix * (int)p.out_pix_stride + p.out_ch_off + n) * 4);
+          if constexpr (LEAN) {      // the same values in the same order, the residual fetched eight at a time (registers)
+            const unsigned r0 = (unsigned)((pix * (int)p.res_pix_stride + p.res_ch_off + n) * 4);
+#pragma unroll
+            for (int rb = 0; rb < 16; rb += 8) {
+              float rv[8];
+#pragma unroll
+              for (int r = 0; r < 8; ++r) {
+                const int c = ((rb + r) & 3) + 8 * ((rb + r) >> 2);
+                rv[r] = p.residual ? __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rres, (int)(c < cm ? r0 + c * res_step : OOB), 0, 0)) : 0.f;
+              }
+#pragma unroll
+              for (int r = 0; r < 8; ++r) {
+                const int c = ((rb + r) & 3) + 8 * ((rb + r) >> 2);
+                float v = acc[tm][tn][rb + r] * out_scale + bv;
+                v = fmaxf(v, v * slope_out) * ps + pt + rv[r];
+                __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), rout, (int)(c < cm ? o0 + c * out_step : OOB), 0, 0);
+                const double vm = c < cm ? (double)v : 0.;
+                st_s += vm; st_q += vm * vm;
+              }
+            }
+          } else {
           float rv[16];
 #pragma unroll
           for (int r = 0; r < 16; ++r) rv[r] = 0.f;
@@ -337,11 +416,12 @@ __global__ __launch_bounds__(256, 2) void conv3x3_halo_f16_kernel(const egne_con
               else pool_keep[r] = fmaxf(pool_keep[r], vp);
             }
           }
+          }
           acc[tm][tn] = (f32x16)(0.f);
         }
         if constexpr (POOL) {
           if (p.pool_out) {
-            const int y = cur.y0 + wrow * WM, Hp = (p.H + 1) >> 1, Wp = (p.W + 1) >> 1;
+            const int y = cur.y0 + wrow_e * WM, Hp = (p.H + 1) >> 1, Wp = (p.W + 1) >> 1;
             const __amdgpu_buffer_rsrc_t rpool = make_rsrc(p.pool_out + (long long)cur.b * Hp * Wp * p.pool_pix_stride,
                                                            (unsigned)Hp * Wp * (unsigned)p.pool_pix_stride * 4u);
             const int xl0 = cur.x0 + 4 * lh;
@@ -362,9 +442,9 @@ __global__ __launch_bounds__(256, 2) void conv3x3_halo_f16_kernel(const egne_con
         //  which turn the whole tensor NaN for those; engine.Plan.overflowed reads the word after the run either way.)
         if (!LAT && NW == 1 && p.stats_ws) {     // one chunk = this wave's rows of this tile (fixed order: deterministic; TP: tiles of the transposed walk)
           st_s += __shfl_xor(st_s, 32); st_q += __shfl_xor(st_q, 32);
-          if (lh == 0 && n < p.Cout_store) {
+          if (lh_e == 0 && n < p.Cout_store) {
             const int tile_in_frame = (cur.y0 / TH) * tiles_x + cur.x0 / TW;
-            double2* w = (double2*)p.stats_ws + ((long long)cur.b * p.stats_nchunk + tile_in_frame * 4 + wave) * p.Cout_store + n;
+            double2* w = (double2*)p.stats_ws + ((long long)cur.b * p.stats_nchunk + tile_in_frame * 4 + wrow_e) * p.Cout_store + n;
             *w = make_double2(st_s, st_q);
           }
         }
@@ -472,6 +552,8 @@ extern "C" int egne_conv3x3_halo_f16_fwd(const egne_conv_desc* dp, const void* f
                "conv_halo_f16: presplit %d: 0, or 3 on a raw slice of whole 32-channel blocks (dilation 1, CoutP 32, three products)", g.presplit);
   if (g.presplit == 3) return launch_hf<2, 1, 1, false, 1, 0, 3, true>(d, (const _Float16*)fhi, (const _Float16*)flo, a_scale, os, st);
   const bool w2 = d.CoutP % 64 == 0;   // wider layers: several 64-wide N tiles along grid.y, each re-stages the halo
+  // 96 outputs (ESF-Net's 60x80 dense block): ONE 96-wide tile -- the halo staged and split once, no MFMAs on 32 padding columns
+  const bool w3 = d.CoutP == 96 && d.dil[0] == 1 && d.f16_products != 1 && !d.pool_out;
   // opt-in: measured equal to the <2,2,1> shape (the rolled tap loop gives back what the halved weight traffic gains)
   static const int nw2 = [] { const char* e = getenv("EGNE_SHALO_NW2"); return e ? atoi(e) : 0; }();
   if (nw2 && w2) {
@@ -500,6 +582,7 @@ extern "C" int egne_conv3x3_halo_f16_fwd(const egne_conv_desc* dp, const void* f
   if (d.dil[0] == 1 && pf == 2) return w2 ? launch_hf<2, 2, 1, false, 1, 2>(d, h, l, a_scale, os, st) : launch_hf<2, 1, 1, false, 1, 2>(d, h, l, a_scale, os, st);
   // plain f16 operands (egne_conv_desc.f16_products = 1): the dilation-1 shapes of the edge network (MSBlock convolutions of stages 3-5, conv2_2)
   if (d.dil[0] == 1 && d.f16_products == 1) return w2 ? launch_hf<2, 2, 1, false, 1, 0, 1>(d, h, l, a_scale, os, st) : launch_hf<2, 1, 1, false, 1, 0, 1>(d, h, l, a_scale, os, st);
+  if (w3) return launch_hf<2, 3, 1, false>(d, h, l, a_scale, os, st);
   if (d.dil[0] == 1) return w2 ? launch_hf<2, 2, 1, false>(d, h, l, a_scale, os, st) : launch_hf<2, 1, 1, false>(d, h, l, a_scale, os, st);
   if (d.dil[0] == 2) return w2 ? launch_hf<2, 2, 2, false>(d, h, l, a_scale, os, st) : launch_hf<2, 1, 2, false>(d, h, l, a_scale, os, st);
   // larger dilations: lattice mode (the dilation-S conv as S*S ordinary convs on sub-lattices)

@@ -113,6 +113,8 @@ extern "C" int egne_conv2d_auto_kind(const egne_conv_query* qp, egne_conv_choice
                q.act == EGNE_ACT_RELU && !q.has_post && (long long)H * W * st0 < (1ll << 29) && (long long)H * W * q.dst_pix_stride < (1ll << 29);
   if (msdil) lattice = false;
   if (q.dyn_scales) s1x1 = ms1x1 = big = lattice = msdil = false;
+  // (the routing rules see the 64-multiple row count; a 96-channel layer that ends on the plain dilation-1 halo kernel -- kind
+  //  EGNE_KIND_F16X3_HALO, three products, no pooled second output -- is then packed and launched 96 wide: engine.ConvLayer.sfrag_coutp)
   const int sfrag_coutp = CoutP <= 64 ? CoutP : (CoutP + 63) / 64 * 64;
   const int split_coutp = (Cout > 64 && G == 1) ? (Cout + 127) / 128 * 128 : CoutP;
   const long long mx_stride = st0 > q.dst_pix_stride ? st0 : q.dst_pix_stride;

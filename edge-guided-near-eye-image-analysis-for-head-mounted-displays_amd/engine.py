@@ -21,6 +21,7 @@ HALO_F16_MAX_COUTP = int(os.environ.get("EGNE_HALO_F16_MAX_COUTP", "256"))
 LATTICE_ENABLED = os.environ.get("EGNE_LATTICE", "1") != "0"   # dilated MSBlock groups as lattice-halo launches
 LAYER_BYTES = {}          # layer name -> algorithmic bytes of its launch(es) (input slices + stored output), for bench.py --layers
 TDPOOL_FUSED = os.environ.get("EGNE_TDPOOL_FUSED", "1") != "0"     # Transition_down: pooling folded into the 1x1's operand load
+TDPOOL_STATS_UNITS = 32768     # ... with statistics from its epilogue: a statistics chunk (one wave's turn) grows beyond one 32-pixel block only while the launch keeps this many chunks; measured against 8192 (chunks of 8 blocks at the flagship shape: too coarse to spread evenly over the waves) in profiles/esf_encoder_tiles_per_layer_table.txt
 HALO_POOL = os.environ.get("EGNE_HALO_POOL", "1") != "0"       # ... and the halo kernel writes pool2 behind conv2_2
 POOL_FUSED = os.environ.get("EGNE_POOL_FUSED", "1") != "0"     # conv1_2 writes pool1 from its epilogue (conv3x3_rs_f16.hip)
 RW_MIN_W = int(os.environ.get("EGNE_RW_MIN_W", "120"))         # streamed-weights form: narrowest map
@@ -219,6 +220,7 @@ class ConvLayer:
         self.split = False      # allow the split-f16 (f16x3) kernel for this layer (frozen nets only)
         self.need_split = False
         self.need_sfrag = False  # fragment-order f16 pack for the split-f16 halo kernel
+        self.halo_wide96 = False  # that kernel's 96-wide tile serves the layer (sfrag_coutp)
         self.need_c4h = False    # fragment pack of the streaming split-f16 first-layer kernel
         self.c4hi = self.c4lo = None
         self.need_m1 = False     # [CoutP][Ktot] hi/lo pack (slices padded to 32) for the LDS-staged multi-slice 1x1 kernel
@@ -253,12 +255,14 @@ class ConvLayer:
         vers = tuple(w._version for w in self.weights) + tuple(
             (b._version if b is not None else -1) for b in (self.biases or [])) + (id(getattr(self, "k_perm", None)),)
         have = (getattr(self, "w40", None) is not None or not getattr(self, "need_c4", False)) and ((self.wp is not None or not self.need_flat) and (self.wf is not None or not self.need_frag)
-                and (self.whi is not None or not self.need_split) and (self.fhi is not None or not self.need_sfrag)
+                and (self.whi is not None or not self.need_split) and (self._sfrag_ready() or not self.need_sfrag)
                 and (self.s1hi is not None or not self.need_s1) and (self.wimg is not None or not self.need_big) and (self.wimg1 is not None or not self.need_big1)
                 and (self.m1hi is not None or not self.need_m1) and (self.c4hi is not None or not self.need_c4h)
                 and (self.bfrag is not None or not self.need_bfrag)
                 and (getattr(self, "b1frag", None) is not None or not getattr(self, "need_b1", False)))
         if self.bp is not None and have and vers == self._versions and self.bp.device == dev:
+            if self.need_sfrag:
+                self._sfrag_select()
             return False
         L = _lib.lib()
         T = self.kh * self.kw
@@ -391,20 +395,43 @@ class ConvLayer:
                                                              self.w_scale, self.whi.data_ptr() + 2 * g * per,
                                                              self.wlo.data_ptr() + 2 * g * per, st), "pack_f16x2")
             if self.need_sfrag:
-                perf = T * self.sfrag_coutp() * kts
-                if self.fhi is None:
-                    self.fhi = torch.empty(self.G * perf, dtype=torch.float16, device=dev)
-                    self.flo = torch.empty(self.G * perf, dtype=torch.float16, device=dev)
-                for g, wd in enumerate(ws):
-                    _lib.check(L.egne_pack_conv_weight_f16frag(wd.data_ptr(), self.Cout, self.Cin, self.kh, self.kw, self.sfrag_coutp(), kts,
-                                                               self.w_scale, self.fhi.data_ptr() + 2 * g * perf,
-                                                               self.flo.data_ptr() + 2 * g * perf, st), "pack_f16frag")
+                # one pack per row count a plan asked for (want_sfrag): a 96-channel layer is packed 96 rows wide for the halo kernel's
+                # 96-wide tile and 128 wide for the role-split kernels -- launch plans made at different map sizes may hold either
+                packs = self._sfrag_packs
+                for cw in packs:
+                    perf = T * cw * kts
+                    if packs[cw] is None:
+                        packs[cw] = (torch.empty(self.G * perf, dtype=torch.float16, device=dev),
+                                     torch.empty(self.G * perf, dtype=torch.float16, device=dev))
+                    for g, wd in enumerate(ws):
+                        _lib.check(L.egne_pack_conv_weight_f16frag(wd.data_ptr(), self.Cout, self.Cin, self.kh, self.kw, cw, kts,
+                                                                   self.w_scale, packs[cw][0].data_ptr() + 2 * g * perf,
+                                                                   packs[cw][1].data_ptr() + 2 * g * perf, st), "pack_f16frag")
+                self._sfrag_select()
         self._versions = vers
         return True
 
+    def want_sfrag(self):
+        """The plan being built launches a kernel that reads the fragment-order f16 pack at the layer's current row count."""
+        self.need_sfrag = True
+        self.__dict__.setdefault("_sfrag_packs", {}).setdefault(self.sfrag_coutp(), None)
+
+    def _sfrag_ready(self):
+        packs = getattr(self, "_sfrag_packs", {})
+        return bool(packs) and all(v is not None for v in packs.values())
+
+    def _sfrag_select(self):
+        """fhi / flo: the pack of the row count the layer was last routed with (a plan reads them right after want_sfrag)."""
+        pk = self._sfrag_packs.get(self.sfrag_coutp())
+        if pk is not None:
+            self.fhi, self.flo = pk
+
     def sfrag_coutp(self):
         """Row count of the fragment-order f16 pack: above 64 channels a multiple of 64, so that the halo kernel runs its
-        64-wide shape (96 channels: two 64-wide tiles instead of three 32-wide ones that each re-stage the halo)."""
+        64-wide shape.  96 channels on the plain dilation-1 halo kernel (``halo_wide96``, set by Plan.conv once the layer is
+        routed there): 96, ONE 96-wide tile -- the halo staged once, no MFMAs on 32 padding columns."""
+        if self.CoutP == 96 and getattr(self, "halo_wide96", False):
+            return 96
         return self.CoutP if self.CoutP <= 64 else (self.CoutP + 63) // 64 * 64
 
     def split_coutp(self):
@@ -1190,6 +1217,7 @@ class Plan:
         # wider inputs: the resident-weights kernel with its weights streamed chunk by chunk (no statistics from its epilogue)
         # (measured against the halo kernel: ahead for 128 -> 32 at 120x160 (290 vs 318 us), level or behind at 60x80 and for wide
         #  outputs -- every output block stages the input again --, so only single-block layers on wide maps take it by default)
+        layer.halo_wide96 = False      # (the routing rules below see the 64-multiple row count; decided once the kernel is known)
         rw_wide = (rs and RW_ENABLED and 64 < pieces[0].Cp <= RW_MAX_CP and layer.sfrag_coutp() <= RW_MAX_COUTP and not stats
                    and W >= (RW_MIN_W_F16 if self.f16_products == 1 else RW_MIN_W) and min(layer.Cout_store, dst.Cp) % 8 == 0 and dst.stride % 4 == 0 and dst.off % 4 == 0
                    and (residual is None or (residual.stride % 4 == 0 and residual.off % 4 == 0)))
@@ -1259,7 +1287,10 @@ class Plan:
             layer.need_c4 = True
             layer.need_flat = True   # the generic pack is still what the backward (wgrad) paths index with kinv
         elif shalo:
-            layer.need_sfrag = True
+            # 96 outputs on the plain halo kernel (three products, dilation 1, no pooled second output): its 96-wide tile
+            layer.halo_wide96 = (layer.CoutP == 96 and not rs and not lattice and not msdil and layer.dils[0] == 1
+                                 and self.f16_products != 1 and getattr(self, "_pool_req", None) is None)
+            layer.want_sfrag()
         elif split and not big:
             layer.need_split = True
         elif halo:
@@ -1716,8 +1747,10 @@ class Plan:
                 and layer.G == 1 and layer.post is None and all(p.scale is not None for p in pieces) and len(pieces) <= _lib.MAXSEG
                 and layer.CoutP <= 96 and G * (layer.CoutP // 32) * 2048 <= 80 * 1024 and dst.Cp % 4 == 0)
 
-    def conv1x1_pooled(self, layer, pieces, dst, B, H, W, name="td"):
-        """dst[B][H/2][W/2] = avg_pool2d(conv1x1(act_in(pieces * scale + shift)), 2) (models/RITnet_v2.py:32-44), one launch."""
+    def conv1x1_pooled(self, layer, pieces, dst, B, H, W, name="td", stats=False):
+        """dst[B][H/2][W/2] = avg_pool2d(conv1x1(act_in(pieces * scale + shift)), 2) (models/RITnet_v2.py:32-44), one launch.
+        ``stats``: InstanceNorm scale / shift of dst (the next dense block's input) in ``last_stats`` -- partial sums from the launch's
+        epilogue where the slice and the LDS budget allow it, a pass over dst otherwise."""
         assert self.td_pool_fusable(layer, pieces, dst), name
         Ho, Wo = H // 2, W // 2
         layer.need_s1 = layer.need_flat = True
@@ -1741,10 +1774,24 @@ class Plan:
         assert tuple(dst.buf.shape[1:3]) == (Ho, Wo), (name, tuple(dst.buf.shape), Ho, Wo)
         self.keep.append(d)
         flops = 2.0 * B * Ho * Wo * layer.Cout * layer.Cin
+        # statistics chunks: runs of 32-pixel blocks of one frame, one wave each (conv1x1_pool_f16x3_kernel) -- as long as the launch
+        # keeps TDPOOL_STATS_UNITS waves busy, at most 8 blocks; + a 32-pixel patch per wave behind the weights in LDS
+        TN = layer.CoutP // 32
+        lds = sum((p.Cp + 15) // 16 for p in pieces) * TN * 2048 + 4 * 32 * 36 * 4
+        fuse_stats = stats and STATS_FUSED and dst.Cp == int(d.Cout_store) and lds <= 80 * 1024
+        if fuse_stats:
+            bpf = (Ho * Wo + 31) // 32
+            cb = max(1, min(8, B * bpf // TDPOOL_STATS_UNITS))
+            nchunk = (bpf + cb - 1) // cb
+            ws = self._stats_ws(d, B, nchunk)
         # normalised operands: the fixed pre-scale of the other fused-affine layers (|x| < 4094 after the InstanceNorm affine)
         self._add(self.L.egne_conv1x1_pool2_f16x3_fwd, (C.byref(d), layer.s1hi.data_ptr(), layer.s1lo.data_ptr(), F16X3_ASCALE, layer.w_scale1),
                   name, flops=flops, kind="conv_f16x3:tdpool1x1", ws=[(4, layer, "w_scale1")])
         LAYER_BYTES[name] = 4.0 * B * (H * W * sum(p.Cp for p in pieces) + Ho * Wo * int(d.Cout_store))
+        if fuse_stats:
+            self.last_stats = self._stats_finish(ws, d, B, Ho * Wo, nchunk, name)
+        elif stats:
+            self.last_stats = self.norm_stats(dst, B, Ho * Wo, name=name + ".stats")[:2]
         return Ho, Wo
 
     def conv_pair(self, l1, pieces, l2, dst, B, H, W, tmp=None, residual=None, name="pair", stats=False, up_add=None):
@@ -1787,7 +1834,7 @@ class Plan:
             assert p.Cp == cp and p.C == c, (name, p.C, p.Cp, c, cp)
         l1.need_s1 = True
         l1.need_flat = True
-        l2.need_sfrag = True
+        l2.want_sfrag()
         for l in (l1, l2):
             if l not in self.layers:
                 self.layers.append(l)
@@ -1853,7 +1900,7 @@ class Plan:
     def _conv_pair_c4(self, l1, src, l2, dst, B, H, W, residual, name, stats):
         l1.need_c4h = True
         l1.need_flat = True
-        l2.need_sfrag = True
+        l2.want_sfrag()
         for l in (l1, l2):
             if l not in self.layers:
                 self.layers.append(l)

@@ -316,7 +316,9 @@ def build_forward_plan(model, B, H, W, dev, training, dtype=torch.float32):
         tin = [d["out"].with_norm(sc2, sh2, ACT_LEAKY), d["x"].with_norm(sc, sh, ACT_LEAKY)]
         if pools[i] and not training and pl.td_pool_fusable(tdl, tin, D[i + 1]["x"]) and h % 2 == 0 and w % 2 == 0:
             # eval plans: the 2x2 average folded into the 1x1's operand load (linear ops commute): one launch, no pooled tensor
-            pl.conv1x1_pooled(tdl, tin, D[i + 1]["x"], NB, h, w, name=nm + ".TD")
+            # ... and the InstanceNorm statistics of the next block's input from its epilogue (no pass over the pooled tensor)
+            pl.conv1x1_pooled(tdl, tin, D[i + 1]["x"], NB, h, w, name=nm + ".TD", stats=True)
+            x_stats = pl.last_stats
         elif pools[i] and (not training or (TD_POOL_FIRST_TRAIN and h % 2 == 0 and w % 2 == 0)):
             # pool first, then the 1x1 conv at quarter resolution (linear ops commute; avg_pool2d drops an odd last row / column
             # on both routes).  Training plans too: the 1x1, its weight and data gradients all run on a quarter of the pixels, and
