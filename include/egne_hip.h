@@ -706,6 +706,26 @@ int egne_spatial_weights(const int64_t* label, int B, int H, int W, float* out, 
  *   implemented: the host wrapper rejects them.  img / out_img uint8 [B,H,W], label / out_label int64 [B,H,W]; not in place. */
 int egne_augment(const uint8_t* img, const int64_t* label, const int32_t* choice, const double* param, const uint8_t* lut,
                  const double* noise, uint8_t* out_img, int64_t* out_label, int B, int H, int W, void* stream);
+/* egne_augment_cv: the OpenCV branches of data_augment.augment (data_augment.py:38-42 cv2.GaussianBlur, :67-79 cv2.line, :99-120
+ *   cv2.getRotationMatrix2D + cv2.warpAffine) over the same batch (csrc/augment_cv.hip; egne_amd.data_augment
+ *   .augment_batch(on_cv2="device") calls it behind egne_augment, in place of the NotImplementedError of the default mode).  out_img /
+ *   out_label must already hold egne_augment's result (a copy for these frames); frames of any other choice are not touched.
+ *   frame int32 [B][3] on the device = {choice, sigma, number of kept segments} per frame, frame_host the same array in HOST memory
+ *   (validated here: sigma 2..6 for choice 1, at most 9 segments for choice 5; H, W >= 4 when a frame is blurred).
+ *   1 cv2.GaussianBlur(img, (7,7), sigma): separable, BORDER_REFLECT_101, taps q8[sigma-2][7] (int32 [5][7], 8-bit fixed point, each
+ *     row sums to 256): r = sum q*src, s = sum q*r, out = (s + 32768) >> 16; label unchanged.
+ *   5 cv2.line(.., 255, thickness 4) for segs[b][j] = (x1, y1, x2, y2), j < kept (float64 [B][9][4], clipped by the host to
+ *     [-4, W+3] x [-4, H+3]): a pixel becomes 255 iff its squared distance to a segment is <= 4.0 (float64, t = clamp(dot / len2, 0, 1),
+ *     a zero-length segment is a disc); label unchanged.
+ *   6 cv2.warpAffine(.., M, flags=INTER_LANCZOS4 / INTER_NEAREST), BORDER_CONSTANT 0: rot[b] = i00 i01 i02 i10 i11 i12 (float64 [B][6])
+ *     is the INVERSE of M; X = ((i00*x) + (i01*y)) + i02, Y likewise.  Image: ix = floor(32*X + 0.5), first tap (ix >> 5) - 3, weights
+ *     phase[ix & 31][8] (float64 [32][8], Lanczos a = 4, normalised), same in y; t[ky] = sum_kx wx*src from 0.0 left to right,
+ *     v = sum_ky wy*t, out = clip(rint(v), 0, 255).  Label: label[floor(Y + 0.5)][floor(X + 0.5)], 0 outside.
+ *   PIXEL PARITY WITH OPENCV UNPINNED (tap rounding of the blur, boundary pixels of the thick line, 15-bit Lanczos weights); the
+ *   kernels are byte-identical to the restatement in tests/augment_cv2_refs.py.  Not in place. */
+int egne_augment_cv(const uint8_t* img, const int64_t* label, const int32_t* frame, const int32_t* frame_host, const double* segs,
+                    const double* rot, const int32_t* q8, const double* phase, uint8_t* out_img, int64_t* out_label, int B, int H,
+                    int W, void* stream);
 
 /* Device-side front and back end of evaluate.py (--device_io 1; csrc/evalio.hip), pinned bit for bit against the host functions there.
  * egne_eval_prep: preprocess_frame(grey, (Ho, Wo), align_width=True) for every eye of a batch of video frames.  src uint8 [N,Hs,Ws];
