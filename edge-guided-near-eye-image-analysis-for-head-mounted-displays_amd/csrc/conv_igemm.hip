@@ -128,7 +128,8 @@ __global__ __launch_bounds__(256) void conv_igemm_kernel(const egne_conv_desc p)
       for (int ky = 0; ky < p.kh; ++ky)
         for (int kx = 0; kx < p.kw; ++kx) {
           const int iy = (pyx[i] >> 16) + (ky - p.pad_h) * dil, ix = (pyx[i] & 0xffff) + (kx - p.pad_w) * dil;
-          if (pb[i] >= 0 && (p.pad_mode == 1 || (iy >= 0 && iy < p.H && ix >= 0 && ix < p.W))) mk |= 1u << (ky * p.kw + kx);
+          const int t = ky * p.kw + kx;      // (a mask word holds 32 taps: larger kernels test the coordinates per step, load_step)
+          if (t < 32 && pb[i] >= 0 && (p.pad_mode == 1 || (iy >= 0 && iy < p.H && ix >= 0 && ix < p.W))) mk |= 1u << t;
         }
       tapmask[i] = mk;
     }
@@ -220,11 +221,23 @@ __global__ __launch_bounds__(256) void conv_igemm_kernel(const egne_conv_desc p)
       }
     } else {
       const int tapd = dy * p.W + dx;
+      if (T > 32) {
+        // more taps than the mask word has bits (the zero-padded 7x7 that is the data gradient of the StyleEncoder's first block,
+        // engine.TransposedLayer): the bounds test per row and step
 #pragma unroll
-      for (int i = 0; i < AR; ++i) {
-        const bool ok = cok && ((tapmask[i] >> s.tap) & 1u);
-        ra[i] = load_raw4<TS>(rin, ok ? (pix[i] + tapd) * ps4 + coff : (int)OOB, 0);
-        okmask |= (ok ? 1u : 0u) << i;
+        for (int i = 0; i < AR; ++i) {
+          const int iy = (pyx[i] >> 16) + dy, ix = (pyx[i] & 0xffff) + dx;
+          const bool ok = cok && pb[i] >= 0 && (unsigned)iy < (unsigned)p.H && (unsigned)ix < (unsigned)p.W;
+          ra[i] = load_raw4<TS>(rin, ok ? (pix[i] + tapd) * ps4 + coff : (int)OOB, 0);
+          okmask |= (ok ? 1u : 0u) << i;
+        }
+      } else {
+#pragma unroll
+        for (int i = 0; i < AR; ++i) {
+          const bool ok = cok && ((tapmask[i] >> s.tap) & 1u);
+          ra[i] = load_raw4<TS>(rin, ok ? (pix[i] + tapd) * ps4 + coff : (int)OOB, 0);
+          okmask |= (ok ? 1u : 0u) << i;
+        }
       }
     }
     const int wstep = (((s.g * T + s.tap) * p.CoutP) * p.Ktot + s.kofs + s.c0) * 4;

@@ -575,3 +575,41 @@ def test_augment_draws_consume_the_random_stream_like_the_reference():
         ch, _, _, _ = DA.draw(1, base.shape, host_noise=True)
         got = np.random.get_state()
         assert ch[0] == min(first, 7) and np.array_equal(want[1], got[1]) and want[2] == got[2]
+
+
+@pytest.mark.parametrize("k,stride,P", [(3, 1, 1), (7, 1, 3), (4, 2, 1), (2, 2, 0)])
+def test_transposed_layer_derived_weights_match_autograd(k, stride, P):
+    """engine.TransposedLayer.refresh on the host: the data gradient of a (reflect-padded and / or stride-2) convolution w.r.t. its
+    PADDED input is an ordinary zero-padded stride-1 convolution over the output gradient with the derived weights -- the stride-1
+    flip, the 4x4 / stride-2 phase packing and the 2x2 / stride-2 phase packing, un-shuffled as the class' docstring states (channel
+    block (a, b) of the launch holds the padded positions (2m + a, 2n + b)) -- against float64 autograd.grad of F.conv2d on 6x8 inputs."""
+    import torch.nn.functional as F
+    from egne_amd.engine import ConvLayer, TransposedLayer
+    g = torch.Generator().manual_seed(100 * k + stride)
+    B, Ci, Co, H, W = 2, 8, 5, 6, 8
+    w = torch.nn.Parameter(torch.randn(Co, Ci, k, k, generator=g))
+    fwd = ConvLayer([w], None, [(Ci, Ci)], stride=stride, pad=(P, P), pad_mode=1 if P else 0)
+    tl = TransposedLayer(fwd, 0, torch.device("cpu"))
+    tl.guard()                                   # as Plan.run does before it packs
+    assert tl.phase == {(3, 1): 0, (7, 1): 0, (4, 2): 1, (2, 2): 2}[(k, stride)]
+    Hp, Wp = H + 2 * P, W + 2 * P
+    xp = torch.zeros(B, Ci, Hp, Wp, dtype=torch.float64, requires_grad=True)
+    y = F.conv2d(xp, w.detach().double(), stride=stride)
+    assert tuple(y.shape[2:]) == fwd.out_hw(H, W)
+    gy = torch.randn(y.shape, generator=g, dtype=torch.float64)
+    (want,) = torch.autograd.grad(y, xp, gy)
+    got = F.conv2d(gy, tl.derived.double(), padding=tl.pad)
+    assert tuple(got.shape[1:]) == (tl.Cout,) + tuple(tl.out_hw(*y.shape[2:]))
+    if tl.phase:
+        # [b][(a, b', ci)][m][n] -> [b][ci][2m + a][2n + b']
+        got = got.view(B, 2, 2, Ci, Hp // 2, Wp // 2).permute(0, 3, 4, 1, 5, 2).reshape(B, Ci, Hp, Wp)
+    assert got.shape == want.shape
+    assert (got - want).abs().max().item() < 1e-12 * want.abs().max().item()
+    # the guard re-derives the tensor when the forward weight changed in place
+    with torch.no_grad():
+        w.mul_(2.0)
+    tl.guard()
+    got2 = F.conv2d(gy, tl.derived.double(), padding=tl.pad)
+    if tl.phase:
+        got2 = got2.view(B, 2, 2, Ci, Hp // 2, Wp // 2).permute(0, 3, 4, 1, 5, 2).reshape(B, Ci, Hp, Wp)
+    assert (got2 - 2 * want).abs().max().item() < 1e-12 * want.abs().max().item()
