@@ -1415,13 +1415,13 @@ static int norm_bwd_impl(const T* x, int64_t xs, int xo, const float* scale, con
   EGNE_REQUIRE((dgamma == nullptr) == (dbeta == nullptr) && (!dgamma || !per_sample), "norm_bwd: dgamma/dbeta only for batch statistics");
   const int Bn = per_sample ? B : 1;
   const long long npix = per_sample ? HW : (long long)B * HW;
+  EGNE_REQUIRE(npix * (Cp / egne_vt<T>::N) < (1ll << 32) && Bn <= 65535, "norm_bwd: more than 2^32 vectors per statistics group");
   const int nchunk = chunks_for(npix, Cp, Bn);
   hipStream_t st = (hipStream_t)stream;
   hipLaunchKernelGGL(norm_bwd_partial<T>, dim3(nchunk, (Cp + 31) / 32, Bn), dim3(256), 0, st, x, (long long)xs, xo, scale, shift,
                      gy, (long long)gs, go, act_in, Cp, npix, nchunk, per_sample, (double*)ws, poolW);
   hipLaunchKernelGGL(norm_bwd_final, dim3((Cp + 31) / 32, Bn), dim3(1024), 0, st, (const double*)ws, Cp, Bn, nchunk, sums,
                      dgamma, dbeta, C);
-  EGNE_REQUIRE(npix * (Cp / egne_vt<T>::N) < (1ll << 32) && Bn <= 65535, "norm_bwd: more than 2^32 vectors per statistics group");
   const long long gxa = grid_for((long long)Bn * npix * (Cp / egne_vt<T>::N));
   hipLaunchKernelGGL(norm_bwd_apply<T>, dim3((unsigned)((gxa + Bn - 1) / Bn), Bn), dim3(256), 0, st, x, (long long)xs, xo,
                      scale, shift, gamma, gy, (long long)gs, go, act_in, Cp, npix, Bn, per_sample, sums, gx, (long long)gxs,

@@ -344,7 +344,8 @@ extern "C" int egne_conv2d_f16_big1_fwd(const egne_conv_desc* dp, const void* wi
   EGNE_REQUIRE(dp && wimg, "conv_f16_big1: null pointer");
   const egne_conv_desc& d = *dp;
   EGNE_REQUIRE(d.f16_products == 1 && d.nseg == 1 && d.ngroups == 1 && d.stride == 1 && d.pad_mode == 0 && !d.seg[0].scale && !d.seg[0].shift &&
-               !d.residual && !d.post_scale && d.kh * d.kw <= 32, "conv_f16_big1: unsupported descriptor");
+               !d.residual && !d.post_scale, "conv_f16_big1: unsupported descriptor");
+  EGNE_REQUIRE(d.kh >= 1 && d.kw >= 1 && d.kh * d.kw <= 32, "conv_f16_big1: %d taps (%dx%d): the per-row tap mask holds 32", d.kh * d.kw, d.kh, d.kw);
   const egne_seg& g = d.seg[0];
   EGNE_REQUIRE(g.ptr && g.Cp % 32 == 0 && g.Cp == d.Ktot && ((uintptr_t)g.ptr & 15) == 0 && g.ch_off % 4 == 0 && g.pix_stride % 4 == 0 &&
                ((g.Cp / 32) * d.kh * d.kw) % 2 == 0, "conv_f16_big1: input slice (Cp %d Ktot %d, an even number of K steps)", g.Cp, d.Ktot);

@@ -453,6 +453,8 @@ int f16x3_impl(const egne_conv_desc* dp, const void* whi, const void* wlo, float
   EGNE_REQUIRE(d.nseg == 1 && d.ngroups >= 1 && d.ngroups <= EGNE_MAXGROUP && d.stride == 1 && d.pad_mode == 0 &&
                (d.seg[0].scale == nullptr) == (d.seg[0].shift == nullptr) && (d.ngroups == 1 || !d.seg[0].scale),
                "conv_f16x3: unsupported descriptor");
+  // (a staged row's in-range taps are one bit each of a 32-bit word: tap 32 would wrap onto tap 0)
+  EGNE_REQUIRE(d.kh >= 1 && d.kw >= 1 && d.kh * d.kw <= 32, "conv_f16x3: %d taps (%dx%d): the per-row tap mask holds 32", d.kh * d.kw, d.kh, d.kw);
   EGNE_REQUIRE(d.seg[0].Cp % 8 == 0 && (d.seg[0].Cp + 31) / 32 * 32 == d.Ktot && d.CoutP % 32 == 0,
                "conv_f16x3: Cp %d Ktot %d (must be Cp rounded up to 32) CoutP %d", d.seg[0].Cp, d.Ktot, d.CoutP);
   EGNE_REQUIRE(d.seg[0].ptr && ((uintptr_t)d.seg[0].ptr & 15) == 0 && d.seg[0].ch_off % 4 == 0 && d.seg[0].pix_stride % 4 == 0,

@@ -384,7 +384,8 @@ extern "C" int egne_conv2d_f16x3_big_fwd(const egne_conv_desc* dp, const void* w
   EGNE_REQUIRE(dp && wimg, "conv_f16x3_big: null pointer");
   const egne_conv_desc& d = *dp;
   EGNE_REQUIRE(d.nseg == 1 && d.ngroups == 1 && d.stride == 1 && d.pad_mode == 0 && !d.seg[0].scale && !d.seg[0].shift && !d.residual &&
-               !d.post_scale && d.kh * d.kw <= 32, "conv_f16x3_big: unsupported descriptor");
+               !d.post_scale, "conv_f16x3_big: unsupported descriptor");
+  EGNE_REQUIRE(d.kh >= 1 && d.kw >= 1 && d.kh * d.kw <= 32, "conv_f16x3_big: %d taps (%dx%d): the per-row tap mask holds 32", d.kh * d.kw, d.kh, d.kw);
   const egne_seg& g = d.seg[0];
   EGNE_REQUIRE(g.ptr && g.Cp % 32 == 0 && g.Cp == d.Ktot && ((uintptr_t)g.ptr & 15) == 0 && g.ch_off % 4 == 0 && g.pix_stride % 4 == 0,
                "conv_f16x3_big: input slice (Cp %d Ktot %d)", g.Cp, d.Ktot);

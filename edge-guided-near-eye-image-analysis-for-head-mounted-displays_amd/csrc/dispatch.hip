@@ -91,7 +91,8 @@ extern "C" int egne_conv2d_auto_kind(const egne_conv_query* qp, egne_conv_choice
   bool smallcin = k3 && q.stride == 1 && G == 1 && same1 && q.pad_mode == 0 && q.nseg == 1 && d0 == 1 && Cin <= 4 && pad8i(Cout) <= 64 && raw &&
                   !q.has_residual && !q.is_dgrad;
   const bool c4h = smallcin && (q.split || q.split_c4) && pad8i(Cout) > 32;          // C4H_MODE "wide"
-  bool split = q.split && q.stride == 1 && q.pad_mode == 0 && q.nseg == 1 && Cp0 >= 32;
+  // (the split-f16 flat / small / big kernels keep a row's in-range taps in a 32-bit mask: a 7x7 falls through to conv_igemm)
+  bool split = q.split && q.stride == 1 && q.pad_mode == 0 && q.nseg == 1 && Cp0 >= 32 && q.kh * q.kw <= 32;
   bool shalo = split && k3 && G == 1 && same1 && d0 <= 2 && W >= (CoutP > 64 ? HALO_F16_MIN_W : HALO_F16_MIN_W_NARROW) && CoutP <= HALO_F16_MAX_COUTP &&
                !q.has_residual && (long long)H * W * st0 < (1ll << 31);
   int minlat = 1 << 30;

@@ -1176,8 +1176,9 @@ class Plan:
         # channels, 7 % slower for 32)
         c4h = (smallcin and F16X3_ENABLED and (layer.split or getattr(layer, "split_c4", False))
                and (C4H_MODE == "all" or (C4H_MODE == "wide" and pad8(layer.Cout) > 32)))
+        # (the split-f16 flat / small / big kernels keep a row's in-range taps in a 32-bit mask: a 7x7 falls through to conv_igemm)
         split = (F16X3_ENABLED and layer.split and layer.stride == 1 and layer.pad_mode == 0 and len(pieces) == 1
-                 and pieces[0].Cp >= 32)
+                 and pieces[0].Cp >= 32 and layer.kh * layer.kw <= 32)
         # narrow 3x3 layers on wide images: split-f16 arithmetic AND the LDS halo (input fetched once for 9 taps)
         shalo = (split and HALO_F16_ENABLED and layer.kh == 3 and layer.kw == 3 and layer.G == 1 and layer.pad == (1, 1)
                  and layer.dils[0] <= 2 and W >= (HALO_F16_MIN_W if layer.CoutP > 64 else HALO_F16_MIN_W_NARROW)

@@ -1,4 +1,5 @@
-"""Plain torch references of the small operations (csrc/adain.hip, elementwise.hip, backward.hip, loss.hip, bdcn_tail.hip).
+"""Plain torch references of the small operations (csrc/adain.hip, elementwise.hip, backward.hip, loss.hip, bdcn_tail.hip): the AdaIN
+path, heads, resampling, normalisation and pooling, losses, the BDCN tail.
 
 Every function computes in the dtype of its inputs: the tests call it once in float64 (the reference) and once in float32 (the
 yardstick a kernel's error is measured against, see ``bound``).  A backward reference is autograd through the forward reference
@@ -152,14 +153,96 @@ def avgpool2_bwd(gy, H, W):
     return torch.einsum("oh,bopc,pw->bhwc", _avg_matrix(H, gy.dtype), gy, _avg_matrix(W, gy.dtype))
 
 
+def _pool_out(n, stride):
+    """Output size of a 2-wide ceil-mode pooling window: the last window must start inside the input."""
+    o = -((n - 2) // -stride) + 1
+    return o - 1 if (o - 1) * stride >= n else o
+
+
 def maxpool2(x, stride):
-    """F.max_pool2d(k=2, stride, ceil_mode=True) of an NHWC tensor."""
-    return F.max_pool2d(x.permute(0, 3, 1, 2), 2, stride, ceil_mode=True).permute(0, 2, 3, 1)
+    """nn.MaxPool2d(2, stride, ceil_mode=True) of an NHWC tensor, window by window: a window that hangs over the border is clipped to
+    the input (what lies outside does not take part, whatever the sign of the data)."""
+    H, W = x.shape[1:3]
+    y0, x0 = torch.arange(_pool_out(H, stride)) * stride, torch.arange(_pool_out(W, stride)) * stride
+    y1, x1 = (y0 + 1).clamp(max=H - 1), (x0 + 1).clamp(max=W - 1)
+    rows = torch.maximum(x[:, y0], x[:, y1])
+    return torch.maximum(rows[:, :, x0], rows[:, :, x1])
 
 
-def affine_act(x, a, b, relu=True):
-    y = x * a + b
-    return torch.relu(y) if relu else y
+def act(x, kind):
+    """The library's activation codes: 0 none, 1 ReLU, 2 LeakyReLU(0.01)."""
+    return torch.relu(x) if kind == 1 else (F.leaky_relu(x, 0.01) if kind == 2 else x)
+
+
+def affine(x, a, b):
+    """x [..., C] * a + b with a, b [C] (or anything that broadcasts)."""
+    return x * a + b
+
+
+def affine_act(x, a, b, relu=True, kind=None):
+    """act(x * a + b); ``kind`` (an activation code) overrides ``relu``."""
+    return act(x * a + b, (1 if relu else 0) if kind is None else kind)
+
+
+# ---- normalisation, pooling, bilinear up-sampling ------------------------------------------------------------------------------------
+def _moments(x, per_sample):
+    """x [B, HW, C]: mean and biased variance over HW of each sample ([B, 1, C]) or over (B, HW) ([1, 1, C]), two passes."""
+    dims = (1,) if per_sample else (0, 1)
+    mean = x.mean(dim=dims, keepdim=True)
+    return mean, ((x - mean) ** 2).mean(dim=dims, keepdim=True)
+
+
+def norm_stats(x, per_sample, eps=1e-5):
+    """x [B, HW, C] -> (scale = rstd, shift = -mean * rstd, mean, biased variance), each [B, C] (per_sample) or [1, C]: InstanceNorm /
+    training-mode BatchNorm statistics.  One spatial element is legal (variance 0)."""
+    mean, var = _moments(x, per_sample)
+    rstd = 1.0 / torch.sqrt(var + eps)
+    return tuple(t[:, 0] for t in (rstd, -mean * rstd, mean, var))
+
+
+def stats_finish(partials, npix, eps=1e-5):
+    """partials [B, nchunk, Cp, 2]: per chunk (sum x, sum x^2) -> (scale, shift, mean, biased variance), each [B, Cp], for samples of
+    npix pixels (a variance that rounds below zero is zero)."""
+    s = partials.sum(dim=1)
+    mean = s[..., 0] / npix
+    var = (s[..., 1] / npix - mean * mean).clamp(min=0)
+    rstd = 1.0 / torch.sqrt(var + eps)
+    return rstd, -mean * rstd, mean, var
+
+
+def norm_fwd(x, gamma, beta, per_sample, act_in, eps=1e-5):
+    """What egne_norm_bwd differentiates (csrc/backward.hip: xh = x * scale + shift, g = gy * act_in'(xh), then gamma): x [B, HW, C];
+    per_sample = 1: act_in(InstanceNorm(x)) (gamma = beta = None); per_sample = 0: act_in(xh) * gamma + beta with the batch's
+    statistics -- a training-mode BatchNorm2d for act_in = 0, the only activation the plans pair with gamma."""
+    mean, var = _moments(x, per_sample)
+    y = act((x - mean) / torch.sqrt(var + eps), act_in)
+    return y if gamma is None else y * gamma + beta
+
+
+def avgpool2(x):
+    """nn.AvgPool2d(2) of an NHWC tensor (floor sizes: an odd last row / column is ignored), summed in row-major order."""
+    Ho, Wo = x.shape[1] // 2, x.shape[2] // 2
+    t, b = x[:, 0:2 * Ho:2], x[:, 1:2 * Ho:2]
+    return (((t[:, :, 0:2 * Wo:2] + t[:, :, 1:2 * Wo:2]) + b[:, :, 0:2 * Wo:2]) + b[:, :, 1:2 * Wo:2]) * 0.25
+
+
+def norm_act_pool2(x, scale, shift, kind):
+    """avgpool2(act(x * scale[n][c] + shift[n][c])): x [B, H, W, C], scale / shift [B, C]."""
+    return avgpool2(act(x * scale[:, None, None, :] + shift[:, None, None, :], kind))
+
+
+def upsample2x(x):
+    """F.interpolate(scale_factor=2, mode='bilinear', align_corners=False) of an NHWC tensor."""
+    H, W = x.shape[1:3]
+    return torch.einsum("oh,bhwc,pw->bopc", _bilinear_matrix(H, x.dtype), x, _bilinear_matrix(W, x.dtype))
+
+
+def act_bwd_bias(g, y, kind):
+    """g * act'(y) with the branch taken from the stored OUTPUT y (y > 0: 1, else the slope: 0 ReLU, 0.01 leaky, 1 none) and its
+    per-channel sums over every leading axis."""
+    slope = {0: 1.0, 1: 0.0, 2: 0.01}[kind]
+    gz = torch.where(y > 0, g, g * slope)
+    return gz, gz.reshape(-1, gz.shape[-1]).sum(dim=0)
 
 
 # ---- losses -----------------------------------------------------------------------------------------------------------------------

@@ -184,6 +184,48 @@ def test_reflect_padded_7x7_fp32(G, H, W, splits):
     _check(_run_layer(G, (3,), 64, (7, 7), H, W, pad=(3, 3), act=1, pad_mode=1), splits)
 
 
+@pytest.mark.parametrize("H,W", [(9, 11), (23, 37)])
+def test_zero_padded_7x7_split_layer_takes_the_implicit_gemm(G, H, W, monkeypatch):
+    """A zero-padded 7x7 (pad 3, 32 -> 32) of a frozen net with layer.split = True: 49 taps do not fit the 32-bit tap mask that the
+    split-f16 flat / small / big kernels keep per staged row, so the planner and egne_conv2d_auto_kind (compared under
+    EGNE_CHECK_DISPATCH) both leave it to conv_igemm, and the split-f16 entry point refuses the descriptor by its tap count.
+    Planned as conv_f16x3:flat / :small the output is wrong by a relative error of order 1 (tap 32 + k aliases tap k)."""
+    import ctypes as C
+    from gpu_util import DEV, to_nhwc_buf
+    from egne_amd import _lib, engine
+    from egne_amd.engine import ConvLayer, Piece, Plan
+    monkeypatch.setattr(engine, "CHECK_DISPATCH", True)
+    B, Cn = 2, 32
+    x = _rand(G, B, Cn, H, W)
+    w, b = _rand(G, Cn, Cn, 7, 7) / (Cn * 49) ** 0.5, _rand(G, Cn)
+    truth = F.conv2d(x.double(), w.double(), b.double(), padding=3)
+    pl = Plan(torch.device(DEV))
+    (px,) = to_nhwc_buf(pl, [x], B, H, W)
+    layer = ConvLayer([torch.nn.Parameter(w.to(DEV))], [torch.nn.Parameter(b.to(DEV))], [(Cn, Cn)], pad=(3, 3))
+    layer.split = True
+    out = pl.buf(B, H, W, Cn + 8)
+    out.fill_(777.0)
+    pl.conv(layer, [px], Piece(out, 8, Cn), B, H, W, name="c7")        # (raises when the two dispatchers disagree)
+    assert _conv_kinds(pl, "c7") == ["conv_igemm"], _conv_kinds(pl, "c7")
+    assert engine.DISPATCH_LOG[-1] == ("c7", "conv_igemm", "conv_igemm"), engine.DISPATCH_LOG[-1]
+    pl.run()
+    torch.cuda.synchronize()
+    assert (out[..., :8] == 777.0).all(), "conv wrote outside its output slice"
+    e = _rel(_nchw(out, 8, Cn), truth)
+    print("zero-padded 7x7 with layer.split on %dx%d: %s, relative error %.2e" % (H, W, _conv_kinds(pl, "c7"), e))
+    assert e < _bound(_conv_kinds(pl, "c7"), "forward"), "forward output: relative error %.2e" % e
+    # the split-f16 entry point on the same descriptor: an error that names the tap count, nothing launched
+    L = _lib.lib()
+    d = pl.calls[-1][1][0]._obj
+    assert (d.kh, d.kw) == (7, 7)
+    wdummy = torch.zeros(64, device=DEV)
+    before = out.clone()
+    rc = L.egne_conv2d_f16x3_fwd(C.byref(d), wdummy.data_ptr(), wdummy.data_ptr(), 1.0, 1.0, _lib.stream_ptr())
+    torch.cuda.synchronize()
+    assert rc != 0 and b"49 taps" in L.egne_last_error(), (rc, L.egne_last_error())
+    assert torch.equal(out, before)
+
+
 @pytest.mark.parametrize("H,W,splits", [(64, 96, "multi"),      # M = 3072
                                         (24, 32, "one")])
 def test_reflect_padded_4x4_stride2_fp32(G, H, W, splits):

@@ -81,6 +81,14 @@ def _sync():
     torch.cuda.synchronize()
 
 
+def _same32(name, a16, a32):
+    """An output that is fp32 in the bf16 twin and in the fp32 kernel (loss terms, parameter sums): 1e-6 of its largest element."""
+    scale = max(a32.abs().max().item(), 1e-30)
+    err = (a16.double() - a32.double()).abs().max().item() / scale
+    print("%s: bf16 twin's fp32 output differs by %.3e (limit 1e-6)" % (name, err))
+    assert err <= 1e-6, "%s: the twin's fp32 output differs by %.3e" % (name, err)
+
+
 # ==== AdaIN fusion path ===============================================================================================================
 @pytest.mark.parametrize("mag", [1.0, 60.0])
 @pytest.mark.parametrize("Cp_out", [3, 8])
@@ -253,6 +261,32 @@ def test_conf_loss_and_backward(lib, B, Cn, flag):
     _check("conf_loss_bwd", _slice(gxb, g0, 0, Cn), r64, r32)
 
 
+@pytest.mark.parametrize("flag", [1, 0])
+@pytest.mark.parametrize("B,Cn", [(1, 2), (6, 4)])
+def test_conf_loss_bf16_twin(lib, B, Cn, flag):
+    """egne_conf_loss_bf16 / egne_conf_loss_bwd_bf16 on the inputs of test_conf_loss_and_backward rounded to bf16: the loss terms are
+    fp32 in both, the gradient differs by one bf16 rounding."""
+    _lib, L, st = lib
+    g = _g(31 + B + Cn)
+    x = _q(torch.randn(B, Cn, generator=g))
+    gt = torch.randint(0, Cn, (B,), generator=g).to(DEV)
+    ld, gld = Cn + 3, Cn + 2
+    gsc = torch.tensor([0.37], device=DEV)
+    outs = []
+    for dt, fw, bw in ((torch.float32, L.egne_conf_loss, L.egne_conf_loss_bwd), (BF, L.egne_conf_loss_bf16, L.egne_conf_loss_bwd_bf16)):
+        xb, terms, gxb = _buf(x, ld, 0, dt), _poison((8,)), _poison((B, gld), dt)
+        terms[0] = 5.0
+        g0 = gxb.clone()
+        _lib.check(fw(xb.data_ptr(), ld, gt.data_ptr(), B, Cn, flag, 2.0, terms.data_ptr(), st))
+        _lib.check(bw(xb.data_ptr(), ld, gt.data_ptr(), B, Cn, flag, gsc.data_ptr(), gxb.data_ptr(), gld, st))
+        _sync()
+        t = terms.cpu()
+        assert (t[1:7] == POISON).all()
+        outs.append((t[[0, 7]], _slice(gxb, g0, 0, Cn)))
+    _same32("conf_loss terms", outs[1][0], outs[0][0])
+    _twin("conf_loss_bwd", outs[1][1], outs[0][1])
+
+
 @pytest.mark.parametrize("P,phase,B,H,W,Cp", [(3, 0, 2, 4, 4, 8), (3, 0, 2, 45, 70, 8), (1, 0, 2, 2, 2, 4), (1, 0, 1, 45, 70, 12),
                                               (1, 1, 2, 2, 2, 8), (1, 1, 2, 46, 70, 8), (3, 0, 2, 240, 320, 112)])
 def test_reflect_pad_backward(lib, P, phase, B, H, W, Cp):
@@ -269,6 +303,25 @@ def test_reflect_pad_backward(lib, P, phase, B, H, W, Cp):
     _lib.check(L.egne_reflect_pad_bwd(gpb.data_ptr(), gs, go, phase, Cp, gxb.data_ptr(), xs, xo, B, H, W, P, st))
     _sync()
     _check("reflect_pad_bwd", _slice(gxb, g0, xo, Cp), pre.double() + R.reflect_pad_bwd(gp.double(), P), pre + R.reflect_pad_bwd(gp, P))
+
+
+@pytest.mark.parametrize("P,phase,B,H,W,Cp", [(1, 0, 2, 2, 2, 4), (3, 0, 2, 45, 70, 8), (1, 1, 2, 46, 70, 8)])
+def test_reflect_pad_backward_bf16_twin(lib, P, phase, B, H, W, Cp):
+    """egne_reflect_pad_bwd_bf16 on the inputs of test_reflect_pad_backward rounded to bf16 (slices at offset 4)."""
+    _lib, L, st = lib
+    g = _g(40 + H + P)
+    gp = _q(torch.randn(B, H + 2 * P, W + 2 * P, Cp, generator=g))
+    pre = _q(torch.randn(B, H, W, Cp, generator=g))
+    src = R.phase_pack(gp) if phase else gp
+    gs, go, xs, xo = src.shape[-1] + 8, 4, Cp + 4, 4
+    outs = []
+    for dt, fn in ((torch.float32, L.egne_reflect_pad_bwd), (BF, L.egne_reflect_pad_bwd_bf16)):
+        gpb, gxb = _buf(src, gs, go, dt), _buf(pre, xs, xo, dt)
+        g0 = gxb.clone()
+        _lib.check(fn(gpb.data_ptr(), gs, go, phase, Cp, gxb.data_ptr(), xs, xo, B, H, W, P, st))
+        _sync()
+        outs.append(_slice(gxb, g0, xo, Cp))
+    _twin("reflect_pad_bwd", outs[1], outs[0])
 
 
 # ==== regression head and latent ======================================================================================================
@@ -342,6 +395,82 @@ def test_spatial_mean_and_backward(lib, Cn, HW, kind):
     _check("spatial_mean_bwd", _slice(gxb, g0, xo, Cn), pre.double() + r64, pre + r32)
 
 
+@pytest.mark.parametrize("n", [1, 512])
+def test_selu_bf16_twin(lib, n):
+    """egne_selu_inplace_bf16 / egne_selu_bwd_bf16 on the inputs of test_selu_and_backward rounded to bf16; both backward kernels read
+    the SAME bf16-representable output."""
+    _lib, L, st = lib
+    g = _g(50 + n % 7)
+    x = torch.linspace(-20, 20, n)[torch.randperm(n, generator=g)] if n > 1 else torch.zeros(1)
+    x[n // 2] = 0.0
+    x, gy = _q(x), _q(torch.randn(n, generator=g))
+    outs = []
+    for dt, fw, bw in ((torch.float32, L.egne_selu_inplace, L.egne_selu_bwd), (BF, L.egne_selu_inplace_bf16, L.egne_selu_bwd_bf16)):
+        xb = _poison((n + 8,), dt)
+        xb[:n] = x.to(DEV).to(dt)
+        _lib.check(fw(xb.data_ptr(), n, st))
+        _sync()
+        y = xb[:n].float().cpu()
+        yin, gb = _poison((n + 8,), dt), _poison((n + 8,), dt)
+        yin[:n] = _q(outs[0][0] if outs else y).to(DEV).to(dt)
+        gb[:n] = gy.to(DEV).to(dt)
+        _lib.check(bw(gb.data_ptr(), yin.data_ptr(), n, st))
+        _sync()
+        assert (xb[n:] == POISON).all() and (gb[n:] == POISON).all()
+        outs.append((y, gb[:n].float().cpu()))
+    _twin("selu", outs[1][0], outs[0][0])
+    _twin("selu_bwd", outs[1][1], outs[0][1])
+
+
+@pytest.mark.parametrize("B", [1, 30])
+def test_ellipse_head_act_bf16_twin(lib, B):
+    """egne_ellipse_head_act_bf16 / egne_ellipse_head_act_bwd_bf16 on the inputs of test_ellipse_head_act_and_backward rounded to bf16
+    (ld = 16: columns 10 .. 15 untouched); both backward kernels read the SAME bf16-representable output."""
+    _lib, L, st = lib
+    g = _g(60 + B)
+    x, gy = _q(2 * torch.randn(B, 10, generator=g)), _q(torch.randn(B, 10, generator=g))
+    outs = []
+    for dt, fw, bw in ((torch.float32, L.egne_ellipse_head_act, L.egne_ellipse_head_act_bwd),
+                       (BF, L.egne_ellipse_head_act_bf16, L.egne_ellipse_head_act_bwd_bf16)):
+        xb = _buf(x, 16, 0, dt)
+        x0 = xb.clone()
+        _lib.check(fw(xb.data_ptr(), B, 16, st))
+        _sync()
+        y = _slice(xb, x0, 0, 10)
+        yin, gb = _buf(_q(outs[0][0] if outs else y), 16, 0, dt), _buf(gy, 16, 0, dt)
+        g0 = gb.clone()
+        _lib.check(bw(gb.data_ptr(), yin.data_ptr(), B, 16, st))
+        _sync()
+        outs.append((y, _slice(gb, g0, 0, 10)))
+    _twin("ellipse_head_act", outs[1][0], outs[0][0])
+    _twin("ellipse_head_act_bwd", outs[1][1], outs[0][1])
+    assert torch.equal(outs[1][0][:, 4], x[:, 4]) and torch.equal(outs[1][1][:, 9], gy[:, 9])
+
+
+@pytest.mark.parametrize("Cn,HW", [(8, 1), (38, 300)])
+def test_spatial_mean_bf16_twin(lib, Cn, HW):
+    """egne_spatial_mean_bf16 (bf16 in, bf16 out) / egne_spatial_mean_bwd_bf16 on the inputs of test_spatial_mean_and_backward rounded
+    to bf16, slices at offset 5."""
+    _lib, L, st = lib
+    B = 2
+    g = _g(70 + Cn + HW)
+    x = _q(torch.randn(B, HW, Cn, generator=g))
+    gm, pre = _q(torch.randn(B, Cn, generator=g)), _q(torch.randn(B, HW, Cn, generator=g))
+    xs, xo = Cn + 9, 5
+    outs = []
+    for dt, fw, bw in ((torch.float32, L.egne_spatial_mean, L.egne_spatial_mean_bwd), (BF, L.egne_spatial_mean_bf16, L.egne_spatial_mean_bwd_bf16)):
+        xb, out = _buf(x, xs, xo, dt), _poison((B * Cn + 8,), dt)
+        _lib.check(fw(xb.data_ptr(), xs, xo, Cn, B, HW, out.data_ptr(), st))
+        gmb, gxb = _buf(gm, Cn + 3, 0, dt), _buf(pre, xs, xo, dt)
+        g0 = gxb.clone()
+        _lib.check(bw(gmb.data_ptr(), Cn + 3, gxb.data_ptr(), xs, xo, Cn, B, HW, st))
+        _sync()
+        assert (out[B * Cn:] == POISON).all()
+        outs.append((out[:B * Cn].float().cpu().reshape(B, Cn), _slice(gxb, g0, xo, Cn)))
+    _twin("spatial_mean", outs[1][0], outs[0][0])
+    _twin("spatial_mean_bwd", outs[1][1], outs[0][1])
+
+
 # ==== resampling and layout ===========================================================================================================
 @pytest.mark.parametrize("B,H,W,Cn", [(1, 1, 1, 8), (3, 15, 20, 40), (2, 120, 160, 64)])
 def test_upsample2x_nearest_and_backward(lib, B, H, W, Cn):
@@ -384,6 +513,48 @@ def test_upsample2x_backward_accumulating_and_storing(lib, H, W):
             _check(name, got, pre.double() + r64, pre + r32)
         else:
             _check(name, got, r64, r32)
+
+
+@pytest.mark.parametrize("B,H,W,Cn", [(1, 1, 1, 8), (3, 15, 20, 40)])
+def test_upsample2x_nearest_bf16_twin(lib, B, H, W, Cn):
+    """egne_upsample2x_nearest_bf16 (exact copies of the bf16 values) / egne_upsample2x_nearest_bwd_bf16 on the inputs of
+    test_upsample2x_nearest_and_backward rounded to bf16, slices at offsets 4 and 8."""
+    _lib, L, st = lib
+    g = _g(80 + H)
+    x, gy, pre = (_q(torch.randn(*shp, generator=g)) for shp in ((B, H, W, Cn), (B, 2 * H, 2 * W, Cn), (B, H, W, Cn)))
+    xs, xo, ys, yo = Cn + 8, 4, Cn + 12, 8
+    outs = []
+    for dt, fw, bw in ((torch.float32, L.egne_upsample2x_nearest, L.egne_upsample2x_nearest_bwd),
+                       (BF, L.egne_upsample2x_nearest_bf16, L.egne_upsample2x_nearest_bwd_bf16)):
+        xb, yb = _buf(x, xs, xo, dt), _poison((B, 2 * H, 2 * W, ys), dt)
+        y0 = yb.clone()
+        _lib.check(fw(xb.data_ptr(), xs, xo, yb.data_ptr(), ys, yo, B, H, W, Cn, st))
+        gyb, gxb = _buf(gy, ys, yo, dt), _buf(pre, xs, xo, dt)
+        g0 = gxb.clone()
+        _lib.check(bw(gyb.data_ptr(), ys, yo, gxb.data_ptr(), xs, xo, B, H, W, Cn, st))
+        _sync()
+        assert torch.equal(_slice(yb, y0, yo, Cn), R.upsample2x_nearest(x))
+        outs.append(_slice(gxb, g0, xo, Cn))
+    _twin("upsample2x_nearest_bwd", outs[1], outs[0])
+
+
+@pytest.mark.parametrize("H,W", [(1, 1), (15, 20)])
+def test_upsample2x_backward_store_bf16_twin(lib, H, W):
+    """egne_upsample2x_bwd_store_bf16 on the inputs of test_upsample2x_backward_accumulating_and_storing rounded to bf16: POISON is
+    overwritten; slices at offset 8 (the twin moves 16-byte vectors: it refuses the fp32 test's offset 4)."""
+    _lib, L, st = lib
+    B, Cn = 2, 16
+    gy = _q(torch.randn(B, 2 * H, 2 * W, Cn, generator=_g(90 + H + W)))
+    outs = []
+    for dt, fn in ((torch.float32, L.egne_upsample2x_bwd_store), (BF, L.egne_upsample2x_bwd_store_bf16)):
+        gyb, gxb = _buf(gy, Cn + 8, 8, dt), _poison((B, H, W, Cn + 16), dt)
+        g0 = gxb.clone()
+        if dt == BF:
+            assert fn(gyb.data_ptr(), Cn + 8, 4, gxb.data_ptr(), Cn + 16, 8, B, H, W, Cn, st) != 0
+        _lib.check(fn(gyb.data_ptr(), Cn + 8, 8, gxb.data_ptr(), Cn + 16, 8, B, H, W, Cn, st))
+        _sync()
+        outs.append(_slice(gxb, g0, 8, Cn))
+    _twin("upsample2x_bwd_store", outs[1], outs[0])
 
 
 @pytest.mark.parametrize("H,W", [(2, 2), (5, 7), (30, 40)])

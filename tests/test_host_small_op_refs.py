@@ -181,3 +181,106 @@ def test_loss_backward_reference_routes_the_iris_centre():
         else:
             assert ge.abs().max() == 0 and gl[:, 0].abs().max() > 0
         assert gl[:, 2].abs().max() > 0 and gl[:, 1].abs().max() == 0
+
+
+# ---- normalisation, pooling, bilinear up-sampling (tests/test_gpu_norm_pool_ops.py) ------------------------------------------------
+def _nchw(t):
+    return t.permute(0, 3, 1, 2)
+
+
+@pytest.mark.parametrize("B,H,W,C", [(2, 3, 5, 4), (3, 8, 6, 7)])
+def test_norm_references_against_instance_and_batch_norm(B, H, W, C):
+    g = _g(20 + H)
+    x = torch.randn(B, H * W, C, generator=g, dtype=D) * 3 + 0.5
+    xc = x.permute(0, 2, 1)                                         # [B, C, HW]
+    gam, bet = torch.randn(C, generator=g, dtype=D) + 1, torch.randn(C, generator=g, dtype=D)
+    # statistics: scale / shift reproduce the normalised tensor, mean / variance are the biased moments
+    for ps in (1, 0):
+        sc, sh, mean, var = R.norm_stats(x, ps)
+        assert sc.shape == ((B, C) if ps else (1, C))
+        want = F.instance_norm(xc, eps=1e-5) if ps else F.batch_norm(xc, None, None, training=True, eps=1e-5)
+        _close((x * sc[:, None] + sh[:, None]).permute(0, 2, 1), want)
+        dims = (2,) if ps else (0, 2)
+        _close(mean, xc.mean(dims).reshape(mean.shape))
+        _close(var, xc.var(dims, unbiased=False).reshape(var.shape))
+        # partial sums of ragged chunks give the same statistics
+        cuts = [0, 1, H * W // 2, H * W]
+        xs = x if ps else x.reshape(1, B * H * W, C)
+        if not ps:
+            cuts = [0, 1, H * W + 2, B * H * W]
+        parts = torch.stack([torch.stack([xs[:, a:b].sum(1), (xs[:, a:b] ** 2).sum(1)], -1) for a, b in zip(cuts, cuts[1:])], 1)
+        for a, b in zip(R.stats_finish(parts, xs.shape[1]), (sc, sh, mean, var)):
+            _close(a, b, 1e-11)
+    # forward whose vjp is the reference of egne_norm_bwd
+    for act_in, fn in ((0, lambda t: t), (1, F.relu), (2, lambda t: F.leaky_relu(t, 0.01))):
+        _close(R.norm_fwd(x, None, None, 1, act_in).permute(0, 2, 1), fn(F.instance_norm(xc, eps=1e-5)))
+    _close(R.norm_fwd(x, gam, bet, 0, 0).permute(0, 2, 1), F.batch_norm(xc, None, None, gam, bet, training=True, eps=1e-5))
+    gy = torch.randn(B, H * W, C, generator=g, dtype=D)
+    xa, ga, ba = xc.clone().requires_grad_(True), gam.clone().requires_grad_(True), bet.clone().requires_grad_(True)
+    want = torch.autograd.grad((F.batch_norm(xa, None, None, ga, ba, training=True, eps=1e-5) * gy.permute(0, 2, 1)).sum(), (xa, ga, ba))
+    got = R.vjp(lambda a, b, c: R.norm_fwd(a, b, c, 0, 0), [x, gam, bet], [gy])
+    _close(got[0].permute(0, 2, 1), want[0])
+    _close(got[1], want[1])
+    _close(got[2], want[2])
+    xa = xc.clone().requires_grad_(True)
+    (want,) = torch.autograd.grad((F.leaky_relu(F.instance_norm(xa, eps=1e-5), 0.01) * gy.permute(0, 2, 1)).sum(), xa)
+    (got,) = R.vjp(lambda a: R.norm_fwd(a, None, None, 1, 2), [x], [gy])
+    _close(got.permute(0, 2, 1), want)
+
+
+def test_norm_stats_reference_takes_a_single_pixel():
+    x = torch.tensor([[[3.0, -2.0]]], dtype=D)
+    sc, sh, mean, var = R.norm_stats(x, 1)
+    assert torch.equal(var, torch.zeros(1, 2, dtype=D)) and torch.equal(mean, x[:, 0])
+    _close(sc, torch.full((1, 2), 1e-5, dtype=D).rsqrt())
+    assert (x[:, 0] * sc + sh).abs().max().item() < 1e-12
+
+
+@pytest.mark.parametrize("B,H,W,C", [(2, 5, 7, 3), (1, 2, 2, 4), (2, 6, 4, 5)])
+def test_pooling_and_affine_references(B, H, W, C):
+    g = _g(30 + H)
+    x = torch.randn(B, H, W, C, generator=g, dtype=D)
+    _close(_nchw(R.avgpool2(x)), F.avg_pool2d(_nchw(x), 2), 1e-15)
+    assert R.avgpool2(x).shape == (B, H // 2, W // 2, C)
+    a, b = torch.randn(C, generator=g, dtype=D), torch.randn(C, generator=g, dtype=D)
+    assert torch.equal(R.affine(x, a, b), x * a + b)
+    assert torch.equal(R.affine_act(x, a, b, kind=2), F.leaky_relu(x * a + b, 0.01))
+    assert torch.equal(R.affine_act(x, a, b), F.relu(x * a + b)) and torch.equal(R.affine_act(x, a, b, False), x * a + b)
+    sc, sh = torch.rand(B, C, generator=g, dtype=D) + 0.5, torch.randn(B, C, generator=g, dtype=D)
+    t = _nchw(x) * sc[:, :, None, None] + sh[:, :, None, None]
+    for kind, fn in ((0, lambda v: v), (1, F.relu), (2, lambda v: F.leaky_relu(v, 0.01))):
+        _close(_nchw(R.norm_act_pool2(x, sc, sh, kind)), F.avg_pool2d(fn(t), 2), 1e-15)
+
+
+@pytest.mark.parametrize("H,W", [(2, 2), (25, 13), (7, 2), (6, 8)])
+@pytest.mark.parametrize("stride", [1, 2])
+def test_maxpool_reference_against_ceil_mode_max_pool2d(H, W, stride):
+    g = _g(40 + H)
+    for x in (torch.randn(2, H, W, 3, generator=g, dtype=D), -1.0 - torch.rand(2, H, W, 3, generator=g, dtype=D),
+              (torch.randn(2, H, W, 3, generator=g, dtype=D) * 2).round() / 2):
+        want = F.max_pool2d(_nchw(x), 2, stride, ceil_mode=True)
+        assert torch.equal(_nchw(R.maxpool2(x, stride)), want)
+
+
+@pytest.mark.parametrize("H,W", [(1, 1), (1, 5), (5, 1), (3, 5)])
+def test_upsample_reference_against_bilinear_interpolate(H, W):
+    x = torch.randn(2, H, W, 3, generator=_g(50 + H + W), dtype=D)
+    _close(_nchw(R.upsample2x(x)), F.interpolate(_nchw(x), scale_factor=2, mode="bilinear", align_corners=False), 1e-15)
+
+
+@pytest.mark.parametrize("shape", [(7, 4), (2, 3, 5, 6)])
+def test_act_bwd_bias_reference_against_autograd(shape):
+    """The masked gradient is autograd of the activation wherever the output is not 0; at y = 0 the kernel's documented branch is the
+    slope (F.leaky_relu's own choice there), for ReLU as well."""
+    g = _g(60 + len(shape))
+    z = torch.randn(*shape, generator=g, dtype=D)
+    z.reshape(-1)[::5] = 0.0
+    gy = torch.randn(*shape, generator=g, dtype=D)
+    for kind, slope in ((0, 1.0), (1, 0.0), (2, 0.01)):
+        za = z.clone().requires_grad_(True)
+        y = F.leaky_relu(za, slope)
+        (want,) = torch.autograd.grad((y * gy).sum(), za)
+        gz, db = R.act_bwd_bias(gy, y.detach(), kind)
+        _close(gz, want, 1e-15)
+        _close(db, want.reshape(-1, shape[-1]).sum(0), 1e-14)
+        assert torch.equal(gz[z == 0], gy[z == 0] * slope)
