@@ -601,8 +601,11 @@ extern "C" int egne_conv2d_fwd(const egne_conv_desc* dp, void* stream) {
   EGNE_REQUIRE(d.out_ch_off + d.Cout_store <= d.out_pix_stride, "conv: output slice exceeds pixel stride");
   EGNE_REQUIRE((d.post_scale == nullptr) == (d.post_shift == nullptr), "conv: post affine mismatch");
   for (int g = 0; g < d.ngroups; ++g) EGNE_REQUIRE(d.dil[g] >= 1, "conv: dilation");
+  // reflect padding mirrors ONCE (load_step): the reach pad * dilation of every group must stay inside the map
   if (d.pad_mode == 1)
-    EGNE_REQUIRE(d.pad_h < d.H && d.pad_w < d.W, "conv: reflect pad larger than input");
+    for (int g = 0; g < d.ngroups; ++g)
+      EGNE_REQUIRE(d.pad_h * d.dil[g] < d.H && d.pad_w * d.dil[g] < d.W, "conv: reflect reach %dx%d (pad %dx%d, dilation %d) not smaller than the input %dx%d",
+                   d.pad_h * d.dil[g], d.pad_w * d.dil[g], d.pad_h, d.pad_w, d.dil[g], d.H, d.W);
   // output size must match the convolution arithmetic for every group (pad scales with dilation)
   for (int g = 0; g < d.ngroups; ++g) {
     int ho = (d.H + 2 * d.pad_h * d.dil[g] - d.dil[g] * (d.kh - 1) - 1) / d.stride + 1;
