@@ -8,6 +8,7 @@ videos/example1.avi) are decoded with PIL, results go to <video>_ellipses.npy in
     python evaluate.py --path2data videos [--max_frames 20]
     python evaluate.py --synthetic 4
     python evaluate.py --path2data videos --low_latency 1 --device_io 1     (frame prep and overlay rendering on the device)
+    python evaluate.py --path2data videos --device_io 1 --device_jpeg 1     (frame number and Motion-JPEG encoding on the device too)
 """
 import argparse
 import glob
@@ -39,7 +40,10 @@ def parse_args(argv=None):
     p.add_argument('--low_latency', type=int, default=0)          # 1: the two eyes of a frame per call, results before the next frame
     p.add_argument('--eye_width', type=int, default=320)          # columns per eye of a video frame (two eyes side by side; evaluate.py:235-249: 320)
     p.add_argument('--device_io', type=int, default=0, choices=(0, 1))   # 1: frame prep and overlay rendering on the device (csrc/evalio.hip)
+    p.add_argument('--device_jpeg', type=int, default=0, choices=(0, 1))  # 1: frame number and JPEG encoding on the device too (csrc/jpeg.hip); needs --device_io 1
     a = p.parse_args(argv)
+    if a.device_jpeg and not a.device_io:
+        p.error('--device_jpeg 1 encodes the frames that --device_io 1 renders on the device: it needs --device_io 1')
     a.prec = torch.float32
     return a
 
@@ -211,15 +215,27 @@ def _upload_u8(frames, device):
 
 
 def _download(t):
-    """The only device -> host copies of --device_io 1 go through here: two uint8 BGR frames and 20 doubles per eye."""
+    """The only device -> host copies of --device_io 1 go through here: two uint8 BGR frames and 20 doubles per eye (with
+    --device_jpeg 1: the streams' lengths and flags, their used bytes in one buffer, and 20 doubles per eye)."""
     return t.cpu().numpy()
+
+
+def _encode_rendered(batch):
+    """--device_jpeg 1, right behind the rendering on its stream: the frame numbers go into a copy of the overlay (a frame whose
+    stream does not fit is drawn by the host from the untouched one), both stacks are encoded."""
+    overlay, edge_frame, _ = batch.rendered
+    stamped = _stamp_masks_device(overlay.clone(), batch.masks)
+    batch.encoded = encode_jpeg_device(stamped) + encode_jpeg_device(edge_frame)
 
 
 class _Batch(list):
     """Frames of a batch whose results are still on the device; with --device_io 1 also their uint8 device copy (kept for the
-    rendering and for a redo) and the rendered tensors once the fit's stream has queued them."""
+    rendering and for a redo) and the rendered tensors once the fit's stream has queued them; with --device_jpeg 1 also the frame
+    numbers' masks on the device and the encoded streams."""
     fu = None
     rendered = None
+    masks = None
+    encoded = None
 
 
 def _to_host(res):
@@ -400,6 +416,175 @@ def render_frames_device(frames_u8, edge, seg, fit, scale_shift, eyes=2, eye_wid
     return overlay, edge_frame, ell
 
 
+# ---- Motion-JPEG on the device (--device_jpeg 1; csrc/jpeg.hip) -- ITU-T T.81 baseline in a JFIF wrapper, tables of its Annex K ---------
+JPEG_RESTART_MCUS = 4          # MCUs (16 x 16 pixels) per restart interval = per wave of the entropy coder: 150 intervals in a 640 x 240 frame
+_JPEG_ZIGZAG = (0, 1, 8, 16, 9, 2, 3, 10, 17, 24, 32, 25, 18, 11, 4, 5, 12, 19, 26, 33, 40, 48, 41, 34, 27, 20, 13, 6, 7, 14, 21, 28,
+                35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23, 30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63)
+_JPEG_LUMA_Q = (16, 11, 10, 16, 24, 40, 51, 61,             # table K.1, rows = vertical frequency
+                12, 12, 14, 19, 26, 58, 60, 55,
+                14, 13, 16, 24, 40, 57, 69, 56,
+                14, 17, 22, 29, 51, 87, 80, 62,
+                18, 22, 37, 56, 68, 109, 103, 77,
+                24, 35, 55, 64, 81, 104, 113, 92,
+                49, 64, 78, 87, 103, 121, 120, 101,
+                72, 92, 95, 98, 112, 100, 103, 99)
+_JPEG_CHROMA_Q = (17, 18, 24, 47, 99, 99, 99, 99,           # table K.2
+                  18, 21, 26, 66, 99, 99, 99, 99,
+                  24, 26, 56, 99, 99, 99, 99, 99,
+                  47, 66, 99, 99, 99, 99, 99, 99) + (99,) * 32
+# tables K.3 - K.6: (number of codes of length 1..16, symbols in code order); an AC symbol is run << 4 | category
+_JPEG_HUFF = (
+    ((0, 1, 5, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0, 0, 0, 0), tuple(range(12))),                                   # DC luminance
+    ((0, 2, 1, 3, 3, 2, 4, 3, 5, 5, 4, 4, 0, 0, 1, 125),                                                    # AC luminance
+     (0x01, 0x02, 0x03, 0x00, 0x04, 0x11, 0x05, 0x12, 0x21, 0x31, 0x41, 0x06, 0x13, 0x51, 0x61, 0x07, 0x22, 0x71,
+      0x14, 0x32, 0x81, 0x91, 0xa1, 0x08, 0x23, 0x42, 0xb1, 0xc1, 0x15, 0x52, 0xd1, 0xf0, 0x24, 0x33, 0x62, 0x72,
+      0x82, 0x09, 0x0a, 0x16, 0x17, 0x18, 0x19, 0x1a, 0x25, 0x26, 0x27, 0x28, 0x29, 0x2a, 0x34, 0x35, 0x36, 0x37,
+      0x38, 0x39, 0x3a, 0x43, 0x44, 0x45, 0x46, 0x47, 0x48, 0x49, 0x4a, 0x53, 0x54, 0x55, 0x56, 0x57, 0x58, 0x59,
+      0x5a, 0x63, 0x64, 0x65, 0x66, 0x67, 0x68, 0x69, 0x6a, 0x73, 0x74, 0x75, 0x76, 0x77, 0x78, 0x79, 0x7a, 0x83,
+      0x84, 0x85, 0x86, 0x87, 0x88, 0x89, 0x8a, 0x92, 0x93, 0x94, 0x95, 0x96, 0x97, 0x98, 0x99, 0x9a, 0xa2, 0xa3,
+      0xa4, 0xa5, 0xa6, 0xa7, 0xa8, 0xa9, 0xaa, 0xb2, 0xb3, 0xb4, 0xb5, 0xb6, 0xb7, 0xb8, 0xb9, 0xba, 0xc2, 0xc3,
+      0xc4, 0xc5, 0xc6, 0xc7, 0xc8, 0xc9, 0xca, 0xd2, 0xd3, 0xd4, 0xd5, 0xd6, 0xd7, 0xd8, 0xd9, 0xda, 0xe1, 0xe2,
+      0xe3, 0xe4, 0xe5, 0xe6, 0xe7, 0xe8, 0xe9, 0xea, 0xf1, 0xf2, 0xf3, 0xf4, 0xf5, 0xf6, 0xf7, 0xf8, 0xf9, 0xfa)),
+    ((0, 3, 1, 1, 1, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0, 0), tuple(range(12))),                                   # DC chrominance
+    ((0, 2, 1, 2, 4, 4, 3, 4, 7, 5, 4, 4, 0, 1, 2, 119),                                                    # AC chrominance
+     (0x00, 0x01, 0x02, 0x03, 0x11, 0x04, 0x05, 0x21, 0x31, 0x06, 0x12, 0x41, 0x51, 0x07, 0x61, 0x71, 0x13, 0x22,
+      0x32, 0x81, 0x08, 0x14, 0x42, 0x91, 0xa1, 0xb1, 0xc1, 0x09, 0x23, 0x33, 0x52, 0xf0, 0x15, 0x62, 0x72, 0xd1,
+      0x0a, 0x16, 0x24, 0x34, 0xe1, 0x25, 0xf1, 0x17, 0x18, 0x19, 0x1a, 0x26, 0x27, 0x28, 0x29, 0x2a, 0x35, 0x36,
+      0x37, 0x38, 0x39, 0x3a, 0x43, 0x44, 0x45, 0x46, 0x47, 0x48, 0x49, 0x4a, 0x53, 0x54, 0x55, 0x56, 0x57, 0x58,
+      0x59, 0x5a, 0x63, 0x64, 0x65, 0x66, 0x67, 0x68, 0x69, 0x6a, 0x73, 0x74, 0x75, 0x76, 0x77, 0x78, 0x79, 0x7a,
+      0x82, 0x83, 0x84, 0x85, 0x86, 0x87, 0x88, 0x89, 0x8a, 0x92, 0x93, 0x94, 0x95, 0x96, 0x97, 0x98, 0x99, 0x9a,
+      0xa2, 0xa3, 0xa4, 0xa5, 0xa6, 0xa7, 0xa8, 0xa9, 0xaa, 0xb2, 0xb3, 0xb4, 0xb5, 0xb6, 0xb7, 0xb8, 0xb9, 0xba,
+      0xc2, 0xc3, 0xc4, 0xc5, 0xc6, 0xc7, 0xc8, 0xc9, 0xca, 0xd2, 0xd3, 0xd4, 0xd5, 0xd6, 0xd7, 0xd8, 0xd9, 0xda,
+      0xe2, 0xe3, 0xe4, 0xe5, 0xe6, 0xe7, 0xe8, 0xe9, 0xea, 0xf2, 0xf3, 0xf4, 0xf5, 0xf6, 0xf7, 0xf8, 0xf9, 0xfa)),
+)
+_JPEG_TABLES, _JPEG_HEADERS = {}, {}
+
+
+def jpeg_tables(quality):
+    """The tables egne_jpeg_encode takes (include/egne_hip.h), as NumPy arrays: (qt uint8 [2,64], the luminance / chrominance divisors
+    in zigzag order -- libjpeg's quality scaling of tables K.1 / K.2 --, huff uint32 [544], (code length << 16) | code of the four
+    Annex K code tables, dct int32 [8,8], T[u][x] = rint(8192 a(u) cos((2x+1) u pi / 16)) computed in float64).  Cached."""
+    quality = int(quality)
+    if not 1 <= quality <= 100:
+        raise ValueError("JPEG quality %d outside 1..100" % quality)
+    if quality not in _JPEG_TABLES:
+        scale = 5000 // quality if quality < 50 else 200 - 2 * quality
+        qt = np.array([[min(max((base[n] * scale + 50) // 100, 1), 255) for n in _JPEG_ZIGZAG] for base in (_JPEG_LUMA_Q, _JPEG_CHROMA_Q)], np.uint8)
+        huff = np.zeros(544, np.uint32)
+        for (counts, symbols), first in zip(_JPEG_HUFF, (0, 32, 16, 288)):
+            code, k = 0, 0
+            for length in range(1, 17):                     # T.81 Annex C: codes of one length are consecutive, then a zero bit is appended
+                for _ in range(counts[length - 1]):
+                    huff[first + symbols[k]] = length << 16 | code
+                    code, k = code + 1, k + 1
+                code <<= 1
+        u, x = np.arange(8, dtype=np.float64)[:, None], np.arange(8, dtype=np.float64)[None, :]
+        a = np.where(u == 0, np.sqrt(1.0 / 8.0), np.sqrt(2.0 / 8.0))
+        dct = np.rint(8192.0 * a * np.cos((2 * x + 1) * u * np.pi / 16)).astype(np.int32)
+        _JPEG_TABLES[quality] = (qt, huff, np.ascontiguousarray(dct))
+    return _JPEG_TABLES[quality]
+
+
+def jpeg_header(W, H, quality, restart_mcus=JPEG_RESTART_MCUS):
+    """Everything of a frame's JPEG file in front of the entropy-coded scan: SOI, APP0 (JFIF 1.1), two DQT, SOF0 (8 bit, H x W, Y 2x2,
+    Cb 1x1, Cr 1x1), the four DHT, DRI, SOS.  ``restart_mcus`` 1..8: what egne_jpeg_encode's LDS staging is sized for.  Cached."""
+    W, H, quality, restart_mcus = int(W), int(H), int(quality), int(restart_mcus)
+    if not (1 <= W <= 65535 and 1 <= H <= 65535 and 1 <= restart_mcus <= 8):
+        raise ValueError("JPEG frame %dx%d / restart interval %d out of range (1..65535, 1..8 MCUs)" % (W, H, restart_mcus))
+    key = (W, H, quality, restart_mcus)
+    if key not in _JPEG_HEADERS:
+        _JPEG_HEADERS[key] = _build_jpeg_header(*key)
+    return _JPEG_HEADERS[key]
+
+
+def _build_jpeg_header(W, H, quality, restart_mcus):
+    qt = jpeg_tables(quality)[0]
+
+    def seg(marker, body):
+        return bytes((0xFF, marker)) + (len(body) + 2).to_bytes(2, 'big') + body
+    h = b'\xff\xd8' + seg(0xE0, b'JFIF\x00\x01\x01\x00\x00\x01\x00\x01\x00\x00')
+    h += seg(0xDB, b'\x00' + qt[0].tobytes()) + seg(0xDB, b'\x01' + qt[1].tobytes())
+    h += seg(0xC0, b'\x08' + H.to_bytes(2, 'big') + W.to_bytes(2, 'big') + bytes((3, 1, 0x22, 0, 2, 0x11, 1, 3, 0x11, 1)))
+    for (counts, symbols), tc_th in zip(_JPEG_HUFF, (0x00, 0x10, 0x01, 0x11)):
+        h += seg(0xC4, bytes((tc_th,)) + bytes(counts) + bytes(symbols))
+    h += seg(0xDD, restart_mcus.to_bytes(2, 'big'))
+    return h + seg(0xDA, bytes((3, 1, 0x00, 2, 0x11, 3, 0x11, 0, 63, 0)))
+
+
+def encode_jpeg_device(frames_bgr_u8, quality=90, cap=None):
+    """Baseline JPEG files of a stack of uint8 BGR device frames [N,H,W,3] (egne_jpeg_encode): returns device tensors (out uint8
+    [N,cap], frame n's file in out[n, :lengths[n]]; lengths int32 [N]; flags int32 [N], 1 where the file did not fit ``cap`` bytes --
+    its length is then 0).  ``cap`` defaults to the header plus 1.5 bytes per pixel of the frame padded to multiples of 16.  Queues on
+    the current stream, no synchronisation."""
+    from egne_amd import _lib
+    from egne_amd.engine import require_cuda
+    f = frames_bgr_u8
+    require_cuda(f, "frames_bgr_u8")
+    if f.dtype != torch.uint8 or f.dim() != 4 or f.shape[3] != 3 or min(f.shape) < 1:
+        raise ValueError("frames_bgr_u8 must be a uint8 [N,H,W,3] tensor")
+    f = f.contiguous()
+    N, H, W = int(f.shape[0]), int(f.shape[1]), int(f.shape[2])
+    header = jpeg_header(W, H, quality, JPEG_RESTART_MCUS)
+    if cap is None:
+        cap = len(header) + (-(-H // 16) * 16) * (-(-W // 16) * 16) * 3 // 2
+    cap = int(cap)
+    if cap < 1:
+        raise ValueError("cap must be positive")
+    qt, huff, dct = _device_table(("jpeg", int(quality)), f.device, lambda: jpeg_tables(quality))
+    hd, = _device_table(("jpeg_header", W, H, int(quality)), f.device, lambda: (np.frombuffer(header, np.uint8).copy(),))
+    L = _lib.lib()
+    out = torch.empty((N, cap), dtype=torch.uint8, device=f.device)
+    lengths = torch.empty(N, dtype=torch.int32, device=f.device)
+    flags = torch.empty(N, dtype=torch.int32, device=f.device)
+    ws = torch.empty(int(L.egne_jpeg_workspace_bytes(N, H, W)), dtype=torch.uint8, device=f.device)
+    _lib.check(L.egne_jpeg_encode(f.data_ptr(), N, H, W, qt.data_ptr(), huff.data_ptr(), dct.data_ptr(), hd.data_ptr(), len(header),
+                                  JPEG_RESTART_MCUS, out.data_ptr(), cap, lengths.data_ptr(), flags.data_ptr(), ws.data_ptr(),
+                                  _lib.stream_ptr()), "jpeg_encode")
+    return out, lengths, flags
+
+
+_STAMP_PATCH = (16, 64, 8, 10)         # rows, columns, x0, y0 of the patch that holds the frame number: asserted per number below
+
+
+def frame_number_mask(j, ph=_STAMP_PATCH[0], pw=_STAMP_PATCH[1], x0=_STAMP_PATCH[2], y0=_STAMP_PATCH[3]):
+    """The coverage mask of _put_frame_number's text: str(j) in white on a black 'L' canvas at (10, 12), same default font; returns
+    the uint8 [ph,pw] patch at origin (x0, y0), which must hold everything PIL draws (asserted)."""
+    from PIL import Image, ImageDraw
+    canvas = Image.new('L', (max(x0 + pw, 0) + 128, max(y0 + ph, 0) + 64), 0)
+    ImageDraw.Draw(canvas).text((10, 12), str(j), fill=255)
+    box = canvas.getbbox()
+    if box is not None and not (x0 <= box[0] and y0 <= box[1] and box[2] <= x0 + pw and box[3] <= y0 + ph and
+                                box[2] < canvas.size[0] and box[3] < canvas.size[1]):
+        raise AssertionError("frame number %r covers %r, outside the %dx%d patch at (%d, %d)" % (j, box, pw, ph, x0, y0))
+    full = np.asarray(canvas)
+    patch = np.zeros((ph, pw), np.uint8)
+    ys, xs = max(y0, 0), max(x0, 0)
+    patch[ys - y0:, xs - x0:] = full[ys: y0 + ph, xs: x0 + pw]
+    return patch
+
+
+def stamp_numbers_device(frames, numbers):
+    """_put_frame_number(frames[n], numbers[n]) on the device, in place (egne_stamp_mask): ``frames`` uint8 [N,H,W,3] BGR on the GPU.
+    The host only draws the numbers' small coverage masks.  Current stream, no synchronisation of the device work."""
+    masks = torch.from_numpy(np.stack([frame_number_mask(j) for j in numbers]))
+    return _stamp_masks_device(frames, masks.to(frames.device))
+
+
+def _stamp_masks_device(frames, masks):
+    from egne_amd import _lib
+    from egne_amd.engine import require_cuda
+    require_cuda(frames, "frames")
+    if frames.dtype != torch.uint8 or frames.dim() != 4 or frames.shape[3] != 3 or not frames.is_contiguous():
+        raise ValueError("frames must be a contiguous uint8 [N,H,W,3] tensor")
+    if masks.dtype != torch.uint8 or masks.dim() != 3 or masks.shape[0] != frames.shape[0]:
+        raise ValueError("one uint8 mask per frame")
+    N, H, W = (int(v) for v in frames.shape[:3])
+    masks = masks.contiguous()
+    _lib.check(_lib.lib().egne_stamp_mask(frames.data_ptr(), N, H, W, masks.data_ptr(), int(masks.shape[1]), int(masks.shape[2]),
+                                          _STAMP_PATCH[2], _STAMP_PATCH[3], 0, 0, 255, _lib.stream_ptr()), "stamp_mask")
+    return frames
+
+
 class MJPEGWriter:
     """Minimal AVI (RIFF) writer with Motion-JPEG frames encoded by PIL -- stands in for cv2.VideoWriter (evaluate.py:219-221;
     the reference writes mp4v, for which there is no encoder in this image).  Frames are BGR uint8 arrays as OpenCV's are."""
@@ -412,6 +597,10 @@ class MJPEGWriter:
         buf = io.BytesIO()
         Image.fromarray(np.ascontiguousarray(frame_bgr[..., ::-1])).save(buf, format='JPEG', quality=90)
         self.frames.append(buf.getvalue())
+
+    def write_jpeg(self, data):
+        """Append a frame that is a complete JPEG file already (encode_jpeg_device)."""
+        self.frames.append(bytes(data))
 
     def release(self):
         import struct
@@ -480,6 +669,9 @@ def evaluate_ellseg_per_video(path_vid, args, model, edge_model, device):
     io = bool(getattr(args, 'device_io', 0))        # frame prep and rendering on the device: uint8 frames up, uint8 frames + ellipses down
     ew = int(getattr(args, 'eye_width', 320))
     live = bool(getattr(args, 'low_latency', 0))    # head-mounted-display use: a frame's ellipses before the next frame arrives
+    dj = bool(getattr(args, 'device_jpeg', 0))      # frame number and JPEG encoding on the device: only the streams' bytes come down
+    if dj and not io:
+        sys.exit('evaluate.py: --device_jpeg 1 needs --device_io 1')
     runner = [None]
 
     def flush():
@@ -519,6 +711,8 @@ def evaluate_ellseg_per_video(path_vid, args, model, edge_model, device):
         batch = _Batch(pending)
         pending.clear()
         batch.fu = _upload_u8(np.stack([fr for _, fr, _ in batch]), device)
+        if dj:
+            batch.masks = torch.from_numpy(np.stack([frame_number_mask(j) for j, _, _ in batch])).to(device)
         if live:
             # prep and rendering are part of the replay: one graph from the uint8 frame to the two uint8 frames
             if runner[0] is None or tuple(runner[0].x.shape) != tuple(batch.fu.shape):
@@ -530,6 +724,8 @@ def evaluate_ellseg_per_video(path_vid, args, model, edge_model, device):
                 if _overflowed(model) | _overflowed(edge_model):
                     raise RuntimeError("non-finite activations after re-calibration: the input frames themselves are not finite")
             batch.rendered = tuple(res)
+            if dj:
+                _encode_rendered(batch)           # eager launches on the same stream, right behind the replay
             done = torch.cuda.Event()
             done.record()
             draw_io(batch, (None, done))
@@ -538,6 +734,8 @@ def evaluate_ellseg_per_video(path_vid, args, model, edge_model, device):
 
         def then(e, m, fit):                  # on the searches' stream, right behind them (WindowedFit.submit)
             batch.rendered = render_frames_device(batch.fu, e, m, fit, ss, 2, ew)
+            if dj:
+                _encode_rendered(batch)
         queued.append(batch)
         r = pipe.submit(x, _seg_and_fit(x, model, wfit, then))
         if r is not None:
@@ -556,19 +754,40 @@ def evaluate_ellseg_per_video(path_vid, args, model, edge_model, device):
             redo[0] = not redo[0]
             torch.cuda.synchronize()
             batch.rendered = evaluate_frames_device_io(batch.fu, model, edge_model, (240, 320), 2, ew)
-        overlay, edge_frame, ell = (_download(t) for t in batch.rendered)
+            if dj:
+                _encode_rendered(batch)
+        if dj:
+            # the lengths and flags of the batch's streams come down, then their used bytes packed into one buffer, then the ellipses
+            out_o, len_o, flag_o, out_e, len_e, flag_e = batch.encoded
+            meta = _download(torch.stack([len_o, flag_o, len_e, flag_e]))
+            packed = _download(torch.cat([o[n, :int(meta[k, n])] for n in range(len(batch)) for k, o in ((0, out_o), (2, out_e))])).tobytes()
+            ell, at = _download(batch.rendered[2]), 0
+        else:
+            overlay, edge_frame, ell = (_download(t) for t in batch.rendered)
         for n, (j, fr, _) in enumerate(batch):
             for i in range(2):
                 q, p = ell[2 * n + i, 0].copy(), ell[2 * n + i, 1].copy()
                 out[j] = (q, p)
                 out[(j, i)] = (q, p)
-            _put_frame_number(overlay[n], j)
+            if not dj:
+                _put_frame_number(overlay[n], j)
             if vid_out is None:
                 Hh, Ww = fr.shape[:2]
                 vid_out = MJPEGWriter(stem + '_result_' + args.method + '.avi', 30, (Ww, Hh))
                 edge_out = MJPEGWriter(stem + '_edge_' + args.method + '.avi', 30, (Ww, Hh))
-            vid_out.write(overlay[n])
-            edge_out.write(edge_frame[n])
+            if not dj:
+                vid_out.write(overlay[n])
+                edge_out.write(edge_frame[n])
+                continue
+            for k, w, frames in ((0, vid_out, batch.rendered[0]), (2, edge_out, batch.rendered[1])):
+                if meta[k + 1, n]:                     # the stream did not fit its slot: the frame itself comes down and PIL encodes it
+                    frame = _download(frames[n])
+                    if k == 0:
+                        _put_frame_number(frame, j)
+                    w.write(frame)
+                else:
+                    w.write_jpeg(packed[at: at + int(meta[k, n])])
+                    at += int(meta[k, n])
 
     def drain():
         r = pipe.flush()

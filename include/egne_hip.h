@@ -756,6 +756,32 @@ int egne_eval_render(const uint8_t* src, int N, int Hs, int Ws, int eyes, int We
                      const double* fit, int Ho, int Wo, double inv_scale, int shift, const double* cos_sin,
                      uint8_t* overlay, uint8_t* edge_frame, double* ell_out, void* stream);
 
+/* Device-side Motion-JPEG encoder and frame-number stamp of evaluate.py (--device_jpeg 1; csrc/jpeg.hip), pinned byte for byte against
+ * the restatement in tests/jpeg_refs.py.  Integer arithmetic throughout: the output is one defined byte string.
+ * egne_jpeg_encode: bgr uint8 [N,H,W,3] (any H, W >= 1) -> frame n's complete baseline JPEG file (T.81, JFIF, 4:2:0) at out + n*cap:
+ *   `header` copied as given (SOI, APP0, two DQT, SOF0 with sampling 2x2 / 1x1 / 1x1, four DHT, DRI = restart_mcus, SOS), the
+ *   entropy-coded scan with RSTm (m cycling 0..7) between restart intervals of restart_mcus (1..8) MCUs, EOI.  lengths[n] = the file's
+ *   size, flags[n] = 0; a file that does not fit `cap` bytes gives lengths[n] = 0, flags[n] = 1 and nothing is written for that frame;
+ *   no byte is ever written outside [out + n*cap, out + n*cap + lengths[n]).
+ *   The frame is extended to multiples of 16 by repeating its last column / row.  Per pixel Y = (19595 R + 38470 G + 7471 B + 32768)
+ *   >> 16, Cb = (-11059 R - 21709 G + 32768 B + 8388608 + 32767) >> 16, Cr = (32768 R - 27439 G - 5329 B + 8388608 + 32767) >> 16;
+ *   chroma = (a + b + c + d + 2) >> 2 of every 2 x 2 group.  F = T s T^t of s = plane - 128 in exact integers, dct = T int32 [8][8],
+ *   T[u][x] = rint(8192 a(u) cos((2x+1) u pi / 16)).  qt uint8 [2][64]: luminance / chrominance divisors q in zigzag order;
+ *   v = sign(F) * ((|F| + (q << 25)) / (q << 26)).  Entropy coding as T.81 F.1.2: MCU = Y00 Y01 Y10 Y11 Cb Cr, DC predictors 0 at
+ *   every interval, ZRL, EOB unless coefficient 63 is non-zero, MSB first, 0x00 behind every 0xFF, last byte filled with 1-bits.
+ *   huff uint32 [544]: entry = (code length << 16) | code; [0,16) DC luminance by category, [16,32) DC chrominance, [32,288) AC
+ *   luminance by (run << 4 | category), [288,544) AC chrominance; unused entries 0.  The tables live on the device and are not
+ *   checked: a code longer than 16 bits gives an undefined stream (never a write outside the slot).  ws: egne_jpeg_workspace_bytes(N, H, W) bytes,
+ *   16-byte aligned.  Bit-identical from run to run.
+ * egne_stamp_mask: blends the grey patch mask[n] (uint8 [N,ph,pw]) at origin (x0, y0), clipped to the frame, into bgr [N,H,W,3] in
+ *   place, as PIL's ImageDraw.text does: per channel t = src*(255 - a) + ink*a + 128, dst = ((t >> 8) + t) >> 8. */
+int64_t egne_jpeg_workspace_bytes(int N, int H, int W);
+int egne_jpeg_encode(const uint8_t* bgr, int N, int H, int W, const uint8_t* qt, const void* huff, const int32_t* dct,
+                     const uint8_t* header, int header_len, int restart_mcus, uint8_t* out, int64_t cap, int32_t* lengths,
+                     int32_t* flags, void* ws, void* stream);
+int egne_stamp_mask(uint8_t* bgr, int N, int H, int W, const uint8_t* mask, int ph, int pw, int x0, int y0, int b, int g, int r,
+                    void* stream);
+
 /*
  * ---- bf16 activation storage (training plans; BASELINE.json configs[2..4], reference loop train.py:262-287, --prec args.py:17-28) ----
  * Twins of the entry points above for plans that keep activations and activation gradients in HBM as bf16 (NHWC, strides and
