@@ -122,6 +122,8 @@ SIGNATURES = {
     "egne_jpeg_workspace_bytes": (i64, [i32, i32, i32]),
     "egne_jpeg_encode": (i32, [vp, i32, i32, i32, vp, vp, vp, vp, i32, i32, vp, i64, vp, vp, vp, vp]),
     "egne_stamp_mask": (i32, [vp, i32, i32, i32, vp, i32, i32, i32, i32, i32, i32, i32, vp]),
+    "egne_jpeg_decode_workspace_bytes": (i64, [i32, i32, i32, i32, i64, i32, i32]),
+    "egne_jpeg_decode": (i32, [vp, i64, vp, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp]),
     "egne_deepvog_loss_workspace_floats": (i64, [i32, i32, i32]),
     "egne_deepvog_loss_fwd": (i32, [vp, i64, i32, vp, vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp]),
     "egne_deepvog_loss_bwd": (i32, [vp, i64, i32, vp, vp, vp, i32, i32, i32, vp, vp, vp, vp, i64, i32, vp]),

@@ -9,11 +9,13 @@ videos/example1.avi) are decoded with PIL, results go to <video>_ellipses.npy in
     python evaluate.py --synthetic 4
     python evaluate.py --path2data videos --low_latency 1 --device_io 1     (frame prep and overlay rendering on the device)
     python evaluate.py --path2data videos --device_io 1 --device_jpeg 1     (frame number and Motion-JPEG encoding on the device too)
+    python evaluate.py --path2data videos --device_io 1 --device_jpeg 1 --device_decode 1     (and the input's Motion-JPEG decoding)
 """
 import argparse
 import glob
 import io
 import os
+import re
 import sys
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -41,9 +43,12 @@ def parse_args(argv=None):
     p.add_argument('--eye_width', type=int, default=320)          # columns per eye of a video frame (two eyes side by side; evaluate.py:235-249: 320)
     p.add_argument('--device_io', type=int, default=0, choices=(0, 1))   # 1: frame prep and overlay rendering on the device (csrc/evalio.hip)
     p.add_argument('--device_jpeg', type=int, default=0, choices=(0, 1))  # 1: frame number and JPEG encoding on the device too (csrc/jpeg.hip); needs --device_io 1
+    p.add_argument('--device_decode', type=int, default=0, choices=(0, 1))  # 1: the input's JPEG decoding on the device (csrc/jpeg_decode.hip); needs --device_io 1
     a = p.parse_args(argv)
     if a.device_jpeg and not a.device_io:
         p.error('--device_jpeg 1 encodes the frames that --device_io 1 renders on the device: it needs --device_io 1')
+    if a.device_decode and not a.device_io:
+        p.error('--device_decode 1 decodes into the frames that --device_io 1 prepares on the device: it needs --device_io 1')
     a.prec = torch.float32
     return a
 
@@ -231,8 +236,9 @@ def _encode_rendered(batch):
 class _Batch(list):
     """Frames of a batch whose results are still on the device; with --device_io 1 also their uint8 device copy (kept for the
     rendering and for a redo) and the rendered tensors once the fit's stream has queued them; with --device_jpeg 1 also the frame
-    numbers' masks on the device and the encoded streams."""
+    numbers' masks on the device and the encoded streams; with --device_decode 1 the decoder's flags (int32 [N], on the device)."""
     fu = None
+    dflags = None
     rendered = None
     masks = None
     encoded = None
@@ -647,6 +653,217 @@ def mjpeg_frames(path):
             continue
 
 
+def mjpeg_chunks(path):
+    """Yield the JPEG files of an MJPEG .avi as byte strings: the SOI/EOI scan of mjpeg_frames, nothing decoded."""
+    data = open(path, 'rb').read()
+    pos = 0
+    while True:
+        a = data.find(b'\xff\xd8\xff', pos)
+        if a < 0:
+            return
+        b = data.find(b'\xff\xd9', a)
+        if b < 0:
+            return
+        pos = b + 2
+        yield data[a:b + 2]
+
+
+def _decode_host(data):
+    """The host path of a frame: PIL, as mjpeg_frames; None where PIL cannot decode it."""
+    from PIL import Image
+    try:
+        return np.array(Image.open(io.BytesIO(data)).convert('L'))
+    except Exception:
+        return None
+
+
+# ---- Motion-JPEG decoding on the device (--device_decode 1; csrc/jpeg_decode.hip) ------------------------------------------------------
+JPEG_GREY, JPEG_444, JPEG_422, JPEG_420 = 0, 1, 2, 3          # `sampling` of egne_jpeg_decode
+JPEG_DESC_BYTES = 1408                                        # one frame's record of egne_jpeg_decode (include/egne_hip.h)
+_JPEG_FOREIGN_MARKER = re.compile(b'\xff[^\x00\xd0-\xd7]')     # in a scan: anything but stuffing and RSTm (a second scan, fill bytes, ...)
+_PARSED_HEADER = [None, None]                                 # the last header jpeg_parse walked, and what it found there
+
+
+def _parse_header(data):
+    """The marker segments of a JPEG file up to and including SOS: a dictionary (see jpeg_parse; 'scan_off' = where the scan starts,
+    'record' = the frame's descriptor without its scan), or None."""
+    n = len(data)
+    if n < 4 or data[:2] != b'\xff\xd8':
+        return None
+    p, qt, huff, restart, sof = 2, {}, {}, 0, None
+    while True:
+        if p + 4 > n or data[p] != 0xFF:
+            return None
+        m = data[p + 1]
+        L = int.from_bytes(data[p + 2: p + 4], 'big')
+        if m in (0x01, 0xD8, 0xD9, 0xFF) or 0xD0 <= m <= 0xD7 or L < 2 or p + 2 + L > n:
+            return None
+        b = data[p + 4: p + 2 + L]
+        if m == 0xDB:
+            for k in range(0, len(b), 65):
+                if b[k] > 3 or k + 65 > len(b):                # 16-bit divisors (Pq = 1), a table number above 3, a short segment
+                    return None
+                qt[b[k]] = b[k + 1: k + 65]
+        elif m == 0xC4:
+            k = 0
+            while k < len(b):
+                if k + 17 > len(b):
+                    return None
+                counts = b[k + 1: k + 17]
+                nsym, code = sum(counts), 0
+                for length in range(16):                       # the codes must fit their lengths (T.81 Annex C)
+                    code = (code + counts[length]) << 1
+                    if code > 2 << (length + 1):
+                        return None
+                if b[k] not in (0x00, 0x01, 0x10, 0x11) or nsym > 256 or k + 17 + nsym > len(b):
+                    return None
+                huff[b[k]] = (bytes(counts), bytes(b[k + 17: k + 17 + nsym]))
+                k += 17 + nsym
+        elif m == 0xC0:
+            if sof is not None or len(b) < 6 or b[0] != 8 or len(b) != 6 + 3 * b[5]:
+                return None
+            sof = (int.from_bytes(b[1:3], 'big'), int.from_bytes(b[3:5], 'big'),
+                   [(b[6 + 3 * i], b[7 + 3 * i] >> 4, b[7 + 3 * i] & 15, b[8 + 3 * i]) for i in range(b[5])])
+        elif 0xC1 <= m <= 0xCF:                                # every other frame type: extended, progressive, lossless, arithmetic
+            return None
+        elif m == 0xDD:
+            if len(b) != 2:
+                return None
+            restart = int.from_bytes(b, 'big')
+        elif m == 0xEE and b[:5] == b'Adobe' and len(b) >= 12 and b[11] != 1:
+            return None                                        # Adobe transform 0 / 2: the components are RGB or YCCK, not YCbCr
+        elif m == 0xDA:
+            break
+        p += 2 + L
+    if sof is None:
+        return None
+    H, W, comps = sof
+    shape = [(h, v) for _, h, v, _ in comps]
+    sampling = {((1, 1),): JPEG_GREY, ((1, 1),) * 3: JPEG_444, ((2, 1), (1, 1), (1, 1)): JPEG_422,
+                ((2, 2), (1, 1), (1, 1)): JPEG_420}.get(tuple(shape))
+    if sampling is None or H < 1 or W < 1:
+        return None
+    if len(comps) == 3 and [c[0] for c in comps] != [1, 2, 3]:   # libjpeg takes other identifiers ('R', 'G', 'B', ...) for other colour spaces
+        return None
+    if sampling in (JPEG_422, JPEG_420) and (W + 1) // 2 <= 2:          # libjpeg replicates chroma planes this narrow
+        return None
+    if len(b) != 4 + 2 * len(comps) or b[0] != len(comps) or tuple(b[-3:]) != (0, 63, 0):
+        return None
+    if not huff:                                               # AVI Motion-JPEG convention: no DHT = the tables of Annex K
+        huff = {ident: (bytes(c), bytes(sy)) for ident, (c, sy) in zip((0x00, 0x10, 0x01, 0x11), _JPEG_HUFF)}
+    sel = []
+    for i, (ident, _, _, tq) in enumerate(comps):
+        td, ta = b[2 + 2 * i] >> 4, b[2 + 2 * i] & 15
+        if b[1 + 2 * i] != ident or td > 1 or ta > 1 or td not in huff or 0x10 | ta not in huff or tq not in qt:
+            return None
+        sel.append((tq, td, ta))
+    record = np.zeros(JPEG_DESC_BYTES, np.uint8)
+    words = record[:32].view(np.int32)
+    words[2] = restart
+    for k in range(3):
+        words[3 + k] = sum(sl[k] << (8 * c) for c, sl in enumerate(sel))
+    for t, body in qt.items():
+        record[32 + 64 * t: 96 + 64 * t] = np.frombuffer(body, np.uint8)
+    tables = []
+    for t, ident in enumerate((0x00, 0x01, 0x10, 0x11)):
+        tables.append(huff.get(ident))
+        if ident in huff:
+            counts, symbols = huff[ident]
+            record[288 + 272 * t: 304 + 272 * t] = np.frombuffer(counts, np.uint8)
+            record[304 + 272 * t: 304 + 272 * t + len(symbols)] = np.frombuffer(symbols, np.uint8)
+    return dict(H=H, W=W, sampling=sampling, components=[(h, v) + sl for (_, h, v, _), sl in zip(comps, sel)],
+                qt={t: bytes(body) for t, body in qt.items()}, huff=tables, restart=restart, scan_off=p + 2 + L, record=record)
+
+
+def jpeg_parse(data):
+    """What egne_jpeg_decode needs of one JPEG file, or None for a file the device decoder does not take (anything but SOF0, 8 bit,
+    one scan, grey or three components at 4:4:4 / 4:2:2 / 4:2:0, 8-bit quantisation tables; fill bytes or foreign markers inside the
+    scan; subsampled chroma planes of one or two columns; three components that are not YCbCr: an Adobe segment with a transform
+    other than 1, or identifiers other than 1, 2, 3).  Walks the marker segments only -- byte-level work, nothing per Huffman
+    symbol.  Returns a dictionary: H, W, sampling (JPEG_GREY / JPEG_444 / JPEG_422 / JPEG_420), components [(h, v, tq, td, ta)],
+    qt {table: 64 bytes in file (zigzag) order}, huff [DC 0, DC 1, AC 0, AC 1] as (16 counts, symbols) or None (a file without DHT
+    gets the tables of Annex K), restart (MCUs, 0 = none), scan_off, scan_len (the entropy-coded scan: up to EOI), record."""
+    hdr, info = _PARSED_HEADER
+    if hdr is None or not data.startswith(hdr):                # (a video's frames mostly share their header byte for byte)
+        info = _parse_header(data)
+        if info is None:
+            return None
+        _PARSED_HEADER[:] = [bytes(data[:info['scan_off']]), info]
+    off = info['scan_off']
+    end = data.find(b'\xff\xd9', off)
+    if end < 0 or _JPEG_FOREIGN_MARKER.search(data, off, end) or data[end - 1: end] == b'\xff':
+        return None
+    return dict(info, scan_len=end - off)
+
+
+def decode_jpeg_device(datas, device=None, sub_bits=1024, mode=1, out=None, parsed=None):
+    """Grey frames of a list of baseline JPEG files (byte strings) decoded on the device (egne_jpeg_decode): returns (grey uint8
+    [N,H,W] on the device -- byte for byte np.asarray(Image.open(...).convert('L')) of every file --, flags int32 [N], non-zero where
+    the scan turned out invalid: that frame's row is then unspecified).  All files share H, W and sampling (ValueError otherwise, and
+    for a file jpeg_parse refuses).  ``mode`` 1: self-synchronising subsequences of ``sub_bits`` bits; 0: one lane per restart
+    interval.  ``out``: the uint8 [N,H,W] device tensor to decode into; ``parsed``: the files' jpeg_parse results, if the caller has
+    them.  One upload of the concatenated scans and one of the descriptor table; queues on the current stream, no synchronisation."""
+    from egne_amd import _lib
+    datas = list(datas)
+    infos = [jpeg_parse(d) for d in datas] if parsed is None else list(parsed)
+    if not datas or len(infos) != len(datas):
+        raise ValueError("decode_jpeg_device needs at least one JPEG file (and one jpeg_parse result per file)")
+    for n, info in enumerate(infos):
+        if info is None:
+            raise ValueError("file %d is not a JPEG stream the device decoder takes (jpeg_parse)" % n)
+    H, W, sampling = infos[0]['H'], infos[0]['W'], infos[0]['sampling']
+    for n, info in enumerate(infos):
+        if (info['H'], info['W'], info['sampling']) != (H, W, sampling):
+            raise ValueError("file %d is %dx%d with sampling %d, file 0 %dx%d with sampling %d: one call, one geometry"
+                             % (n, info['H'], info['W'], info['sampling'], H, W, sampling))
+    N = len(datas)
+    desc = np.stack([info['record'] for info in infos])
+    words = desc[:, :32].view(np.int32)
+    parts, at = [], 0
+    for n, (d, info) in enumerate(zip(datas, infos)):
+        scan = d[info['scan_off']: info['scan_off'] + info['scan_len']]
+        words[n, 0], words[n, 1] = at, len(scan)
+        parts += [scan, b'\0' * (-len(scan) % 4)]
+        at += len(scan) + (-len(scan) % 4)
+    nbytes = max(at, 4)
+    device = torch.device('cuda' if device is None else device)
+    streams = torch.from_numpy(np.frombuffer(b''.join(parts).ljust(nbytes, b'\0'), np.uint8).copy()).to(device)
+    desc = torch.from_numpy(desc).to(device)
+    if out is None:
+        out = torch.empty((N, H, W), dtype=torch.uint8, device=device)
+    elif out.dtype != torch.uint8 or tuple(out.shape) != (N, H, W) or not out.is_contiguous() or out.device.type != 'cuda':
+        raise ValueError("out must be a contiguous uint8 [%d,%d,%d] tensor on the device" % (N, H, W))
+    L = _lib.lib()
+    flags = torch.empty(N, dtype=torch.int32, device=device)
+    ws = torch.empty(int(L.egne_jpeg_decode_workspace_bytes(N, H, W, sampling, nbytes, int(sub_bits), 1)), dtype=torch.uint8, device=device)
+    _lib.check(L.egne_jpeg_decode(streams.data_ptr(), nbytes, desc.data_ptr(), N, H, W, sampling, int(sub_bits), int(mode), out.data_ptr(),
+                                  None, flags.data_ptr(), None, ws.data_ptr(), _lib.stream_ptr()), "jpeg_decode")
+    return out, flags
+
+
+def _decode_batch(batch, device):
+    """--device_decode 1: the frames of a batch into one uint8 [N,H,W] device tensor -- those jpeg_parse took by the device decoder
+    (straight into the tensor when that is all of them), the others from the host's decode.  Returns (frames, flags int32 [N])."""
+    first = next((x[1] for _, fr, x in batch if fr is None), None)
+    shape = (first['H'], first['W']) if first is not None else batch[0][1].shape[:2]
+    on_dev = [n for n, (_, fr, _) in enumerate(batch) if fr is None]
+    fu = torch.empty((len(batch),) + tuple(shape), dtype=torch.uint8, device=device)
+    flags = torch.zeros(len(batch), dtype=torch.int32, device=device)
+    if on_dev:
+        whole = len(on_dev) == len(batch)
+        grey, fl = decode_jpeg_device([batch[n][2][0] for n in on_dev], device, out=fu if whole else None,
+                                      parsed=[batch[n][2][1] for n in on_dev])
+        if whole:
+            return fu, fl
+        at = torch.tensor(on_dev, device=device)
+        fu[at] = grey
+        flags[at] = fl
+    for n, (_, fr, _) in enumerate(batch):
+        if fr is not None:
+            fu[n] = _upload_u8(fr, device)
+    return fu, flags
+
+
 def evaluate_ellseg_per_video(path_vid, args, model, edge_model, device):
     """evaluate.py:195-308: every frame of the video holds two eyes side by side (320 columns each): per eye preprocess ->
     edge -> seg -> fitted ellipses -> back to the source geometry; writes <name>_result_<method>.avi (overlay: class colours,
@@ -672,6 +889,9 @@ def evaluate_ellseg_per_video(path_vid, args, model, edge_model, device):
     dj = bool(getattr(args, 'device_jpeg', 0))      # frame number and JPEG encoding on the device: only the streams' bytes come down
     if dj and not io:
         sys.exit('evaluate.py: --device_jpeg 1 needs --device_io 1')
+    dd = bool(getattr(args, 'device_decode', 0))    # the input's JPEG decoding on the device: compressed bytes up instead of frames
+    if dd and not io:
+        sys.exit('evaluate.py: --device_decode 1 needs --device_io 1')
     runner = [None]
 
     def flush():
@@ -707,18 +927,42 @@ def evaluate_ellseg_per_video(path_vid, args, model, edge_model, device):
         while len(ready) > 1:
             draw(*ready.pop(0))
 
+    def fix_flagged(batch):
+        """--device_decode 1: the decoder's flags come down; a flagged frame is decoded by the host into its row.  True if there was one."""
+        bad = np.flatnonzero(_download(batch.dflags))
+        for n in bad:
+            fr = _decode_host(batch[n][2][0])
+            if fr is None or tuple(fr.shape) != tuple(batch.fu.shape[1:]):
+                sys.exit('evaluate.py: frame %d of %s is a JPEG stream that neither the device decoder nor the host decodes; '
+                         'run with --device_decode 0, which skips such frames' % (batch[n][0], path_vid))
+            torch.cuda.synchronize()
+            batch.fu[n] = _upload_u8(fr, device)
+        if len(bad):
+            batch.dflags.zero_()
+        return len(bad) > 0
+
     def flush_io():
         batch = _Batch(pending)
         pending.clear()
-        batch.fu = _upload_u8(np.stack([fr for _, fr, _ in batch]), device)
+        if dd:
+            # eager launches on this stream, in front of prep (and of the graph replay): stream lengths vary, so nothing is captured
+            batch.fu, batch.dflags = _decode_batch(batch, device)
+        else:
+            batch.fu = _upload_u8(np.stack([fr for _, fr, _ in batch]), device)
         if dj:
             batch.masks = torch.from_numpy(np.stack([frame_number_mask(j) for j, _, _ in batch])).to(device)
         if live:
             # prep and rendering are part of the replay: one graph from the uint8 frame to the two uint8 frames
+            # (--device_decode 1: a capture calibrates on its frames, so it never sees a flagged frame's unspecified row; a replay may,
+            # and what such a row does to the network is either an overflow, answered here, or nothing, answered at draw time)
             if runner[0] is None or tuple(runner[0].x.shape) != tuple(batch.fu.shape):
+                if dd:
+                    fix_flagged(batch)
                 runner[0] = graphed_runner_io(batch.fu, model, edge_model, (240, 320), 2, ew)
             res = runner[0](batch.fu)
             if _overflowed(model) | _overflowed(edge_model):
+                if dd:
+                    fix_flagged(batch)
                 runner[0] = graphed_runner_io(batch.fu, model, edge_model, (240, 320), 2, ew)
                 res = runner[0](batch.fu)
                 if _overflowed(model) | _overflowed(edge_model):
@@ -749,9 +993,14 @@ def evaluate_ellseg_per_video(path_vid, args, model, edge_model, device):
         done.synchronize()
         if res is not None:
             res[2].synchronize()        # WindowedFit.Handle: queues the searches (and the rendering behind them) if their window never opened
-        if redo[0] or _overflowed(model) | _overflowed(edge_model):
-            # as draw(): this batch and the one queued behind it again, from the retained uint8 device frames, rendered again
+        again = redo[0] or _overflowed(model) | _overflowed(edge_model)
+        if again:
             redo[0] = not redo[0]
+        if dd and fix_flagged(batch):
+            # the decoder's flags come down with the results: a flagged frame is decoded by the host, and the batch is done again
+            again = True
+        if again:
+            # as draw(): this batch and the one queued behind it again, from the retained uint8 device frames, rendered again
             torch.cuda.synchronize()
             batch.rendered = evaluate_frames_device_io(batch.fu, model, edge_model, (240, 320), 2, ew)
             if dj:
@@ -772,7 +1021,7 @@ def evaluate_ellseg_per_video(path_vid, args, model, edge_model, device):
             if not dj:
                 _put_frame_number(overlay[n], j)
             if vid_out is None:
-                Hh, Ww = fr.shape[:2]
+                Hh, Ww = (int(v) for v in batch.fu.shape[1:]) if dd else fr.shape[:2]      # (--device_decode 1: from the parsed header)
                 vid_out = MJPEGWriter(stem + '_result_' + args.method + '.avi', 30, (Ww, Hh))
                 edge_out = MJPEGWriter(stem + '_edge_' + args.method + '.avi', 30, (Ww, Hh))
             if not dj:
@@ -827,13 +1076,33 @@ def evaluate_ellseg_per_video(path_vid, args, model, edge_model, device):
             vid_out.write(overlay)
             edge_out.write(edge_frame)
 
-    for j, fr in enumerate(mjpeg_frames(path_vid)):
+    def frames_or_chunks():
+        """--device_decode 1: (None, (file, jpeg_parse's result)) for a frame the device decodes, (host-decoded frame, (file, None)) for
+        one it does not take (or whose geometry is not the video's first device frame's); a file PIL cannot decode either is skipped,
+        as mjpeg_frames skips it, so both paths number the frames alike."""
+        if not dd:
+            yield from mjpeg_frames(path_vid)
+            return
+        key = None
+        for chunk in mjpeg_chunks(path_vid):
+            info = jpeg_parse(chunk)
+            if info is not None:
+                key = key or (info['H'], info['W'], info['sampling'])
+                if (info['H'], info['W'], info['sampling']) == key:
+                    yield None, (chunk, info)
+                    continue
+            fr = _decode_host(chunk)
+            if fr is not None:
+                yield fr, (chunk, None)
+
+    for j, fr in enumerate(frames_or_chunks()):
         if args.max_frames and j >= args.max_frames:
             break
         if io:
             if not args.align_width:
                 sys.exit('Height alignment not implemented! Exiting ...')
-            pending.append((j, fr, None))       # the decoded frame as it is: prep and rendering run on the device
+            # the decoded frame as it is (--device_decode 1: the compressed one): prep and rendering run on the device
+            pending.append((j,) + fr if dd else (j, fr, None))
         else:
             frame_bgr = np.stack([fr] * 3, axis=2)
             eyes = []

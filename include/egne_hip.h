@@ -782,6 +782,51 @@ int egne_jpeg_encode(const uint8_t* bgr, int N, int H, int W, const uint8_t* qt,
 int egne_stamp_mask(uint8_t* bgr, int N, int H, int W, const uint8_t* mask, int ph, int pw, int x0, int y0, int b, int g, int r,
                     void* stream);
 
+/* Device-side Motion-JPEG decoder of evaluate.py (--device_decode 1; csrc/jpeg_decode.hip, csrc/jpeg_decode_core.h): the scans of N
+ * baseline JPEG files (T.81 SOF0, 8 bit, one scan, Huffman) -> grey frames, byte for byte what libjpeg-turbo's default decode path
+ * (jidctint "islow", fancy upsampling) followed by PIL's convert('L') gives; pinned against the restatement in
+ * tests/jpeg_decode_refs.py, which tests/test_host_jpeg_decode.py holds against PIL.  Integer arithmetic with arithmetic shifts
+ * throughout.  The host parses the marker segments (evaluate.jpeg_parse) and does nothing per Huffman symbol.
+ * egne_jpeg_decode: streams = the entropy-coded scans (everything between SOS and EOI: 0x00 stuffing and RSTm still inside) of all
+ *   frames in one buffer of stream_bytes bytes (a multiple of 4), every scan at a multiple of 4, the scans disjoint and in the frames'
+ *   order (scan_off + scan_len of frame n <= scan_off of frame n+1: the per-frame slots of the workspace are placed by scan_off, and
+ *   only each record alone is checked on the device -- records that overlap or run backwards stay in bounds but decode wrongly);
+ *   all frames share H, W and `sampling`:
+ *   0 grey (one component, MCU = one block), 1 = 4:4:4, 2 = 4:2:2 (Y 2x1), 3 = 4:2:0 (Y 2x2); chroma components 1x1, MCU = the Y blocks
+ *   in raster order, Cb, Cr.  desc: one record of 1408 bytes per frame --
+ *     int32 [8]: scan_off, scan_len (bytes), restart interval in MCUs (0 = none), tq, td, ta (byte c of each = the quantisation / DC /
+ *       AC table of component c), 0, 0;
+ *     uint8 [4][64] from byte 32: the quantisation tables 0..3 in file (zigzag) order;
+ *     uint8 [4][272] from byte 288: the code tables DC 0, DC 1, AC 0, AC 1, each 16 counts (codes of length 1..16) + 256 symbols.
+ *   A record is checked on the device (range of the scan, alignment, restart interval); a bad one only flags its frame.
+ *   Stages: (a) per frame, the byte behind every 0xFF is dropped (and the 0xFF too where that byte is RSTm: a segment starts there; a
+ *   frame without restart interval is one segment, whose start state is known: byte-aligned, DC predictors 0, first block of an MCU);
+ *   (b) entropy decode, T.81 F.2.2: mode 0 = one lane walks one segment from start to end -- the form this contract is stated in;
+ *   mode 1 = every segment is cut into subsequences of sub_bits bits (a multiple of 32 in 128..4096) that lanes decode from guessed
+ *   states and re-decode from their left neighbour's exit state until a workgroup-wide vote finds nothing changed (at most one round
+ *   per subsequence; one workgroup per frame, 256 subsequences at a time, no waiting between workgroups): the result is exactly mode
+ *   0's for every stream, valid or not in its bits.  Bits beyond the end of the frame's scan read as 1.  (c) coefficient k of a block
+ *   times q[k], IDCT islow (CONST_BITS 13, PASS1_BITS 2: columns descaled by 11, rows by 18, DESCALE(x, n) = (x + (1 << (n-1))) >> n)
+ *   in 64 bits, clip(x + 128); chroma planes cropped to ceil(H/v) x ceil(W/h) and upsampled with replicated edges -- 4:2:0: s = 3 *
+ *   nearer row + the row above (even output rows) / below (odd), out[2i] = (3 s[i] + s[i-1] + 8) >> 4, out[2i+1] = (3 s[i] + s[i+1] +
+ *   7) >> 4; 4:2:2: out[2i] = (3 c[i] + c[i-1] + 1) >> 2, out[2i+1] = (3 c[i] + c[i+1] + 2) >> 2 --; with cb, cr centred on 0: R =
+ *   clip(Y + ((91881 cr + 32768) >> 16)), G = clip(Y + ((-22554 cb + 32768 - 46802 cr) >> 16)), B = clip(Y + ((116130 cb + 32768) >>
+ *   16)), L = (19595 R + 38470 G + 7471 B + 32768) >> 16; grey streams: L = Y.  (libjpeg replicates instead of interpolating chroma
+ *   planes of one or two columns: evaluate.jpeg_parse leaves such files to the host.)
+ *   grey_out uint8 [N,H,W].  flags int32 [N]: 0, or 1 for a frame with a bad record, a code no table holds, a DC category above 11 or
+ *   AC category above 10, a run that is neither ZRL nor EOB with category 0, a zigzag index past 63, a symbol that ends behind its
+ *   segment, a segment with fewer blocks than it must hold or with more than 7 bits behind its last block, or a count of RSTm that
+ *   is not the segments' minus one; such a frame's row of grey_out (and of coef_out) is unspecified, and nothing outside frame n's
+ *   rows is ever written for frame n.  coef_out (optional, may be NULL; for the tests) int16 [N, blocks, 64]: the quantised
+ *   coefficients in zigzag order after DC prediction, blocks in MCU order.  stats (optional, may be NULL; for the tests) int32 [N,2]:
+ *   (synchronisation rounds of the frame's deepest window -- 0 in mode 0 --, subsequences; mode 0: segments).  ws:
+ *   egne_jpeg_decode_workspace_bytes(N, H, W, sampling, stream_bytes, sub_bits, coef_out == NULL) bytes, 16-byte aligned.  Bit-identical
+ *   from run to run and between the modes and all values of sub_bits. */
+int64_t egne_jpeg_decode_workspace_bytes(int N, int H, int W, int sampling, int64_t stream_bytes, int sub_bits, int own_coef);
+int egne_jpeg_decode(const uint8_t* streams, int64_t stream_bytes, const uint8_t* desc, int N, int H, int W, int sampling,
+                     int sub_bits, int mode, uint8_t* grey_out, int16_t* coef_out, int32_t* flags, int32_t* stats, void* ws,
+                     void* stream);
+
 /*
  * ---- bf16 activation storage (training plans; BASELINE.json configs[2..4], reference loop train.py:262-287, --prec args.py:17-28) ----
  * Twins of the entry points above for plans that keep activations and activation gradients in HBM as bf16 (NHWC, strides and
