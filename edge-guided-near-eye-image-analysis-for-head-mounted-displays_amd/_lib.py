@@ -200,6 +200,8 @@ SIGNATURES = {
     "egne_pack_conv_weight_dgrad": (i32, [vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp, vp]),
     "egne_ellipse_fit": (i32, [vp, i32, vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp]),
     "egne_ellipse_init_from_pred": (i32, [vp, i32, i32, i32, vp, vp, vp, vp]),
+    "egne_mask_seed_workspace_bytes": (i64, [i32, i32, i32]),
+    "egne_ellipse_init_from_mask": (i32, [vp, i32, vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp]),
     "egne_ellipse_iou_counts": (i32, [vp, i32, vp, vp, i32, i32, i32, vp, vp, vp, vp, i32, vp]),
     "egne_last_error": (C.c_char_p, []),
     "egne_version": (i32, []),

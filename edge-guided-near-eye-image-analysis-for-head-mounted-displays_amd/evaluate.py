@@ -10,6 +10,7 @@ videos/example1.avi) are decoded with PIL, results go to <video>_ellipses.npy in
     python evaluate.py --path2data videos --low_latency 1 --device_io 1     (frame prep and overlay rendering on the device)
     python evaluate.py --path2data videos --device_io 1 --device_jpeg 1     (frame number and Motion-JPEG encoding on the device too)
     python evaluate.py --path2data videos --device_io 1 --device_jpeg 1 --device_decode 1     (and the input's Motion-JPEG decoding)
+    python evaluate.py --path2data videos --ellipse_seed mask     (ellipse seeds from the class map instead of the regression head)
 """
 import argparse
 import glob
@@ -25,7 +26,7 @@ from egne_amd import _entry  # noqa: E402
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
-from egne_amd.utils import fit_ellipses_from_pred  # noqa: E402
+from egne_amd.utils import fit_ellipses_from_mask, fit_ellipses_from_pred  # noqa: E402
 
 
 def parse_args(argv=None):
@@ -44,6 +45,7 @@ def parse_args(argv=None):
     p.add_argument('--device_io', type=int, default=0, choices=(0, 1))   # 1: frame prep and overlay rendering on the device (csrc/evalio.hip)
     p.add_argument('--device_jpeg', type=int, default=0, choices=(0, 1))  # 1: frame number and JPEG encoding on the device too (csrc/jpeg.hip); needs --device_io 1
     p.add_argument('--device_decode', type=int, default=0, choices=(0, 1))  # 1: the input's JPEG decoding on the device (csrc/jpeg_decode.hip); needs --device_io 1
+    p.add_argument('--ellipse_seed', type=str, default='pred', choices=('pred', 'mask'))   # mask: the searches are seeded from the class map (csrc/mask_seed.hip)
     a = p.parse_args(argv)
     if a.device_jpeg and not a.device_io:
         p.error('--device_jpeg 1 encodes the frames that --device_io 1 renders on the device: it needs --device_io 1')
@@ -120,9 +122,28 @@ def preprocess_frame(img, op_shape, align_width=True):
     return torch.from_numpy(img).unsqueeze(0).to(torch.float32), scale_shift
 
 
+SEED_REGIONS = {'ritnet_v2': None,                          # utils.DEFAULT_SEED_REGIONS: iris = classes 1 | 2 scored against 1, pupil = class 2
+                'deepvog': ((0, 1), (0b010, 1))}            # class map {0, 1 = pupil}: no iris row, the pupil seeded from and scored against class 1
+
+
+def seed_of(args):
+    """(seed, regions) of --ellipse_seed / --model: ('pred', None) unless the flag asks for the class map."""
+    if args is None or getattr(args, 'ellipse_seed', 'pred') != 'mask':
+        return 'pred', None
+    return 'mask', SEED_REGIONS.get(getattr(args, 'model', 'ritnet_v2'))
+
+
+def _fit(mask, elPred, seed, regions):
+    if seed == 'mask':
+        return fit_ellipses_from_mask(mask, regions)
+    return fit_ellipses_from_pred(mask, elPred)
+
+
 def evaluate_ellseg_on_image(frames, model, edge_model, args=None):
     """evaluate.py:112-166 for a batch of frames [N,1,H,W] (the reference loops one frame at a time).
-    Returns edge maps [N,H,W], class maps [N,H,W], pupil ellipses [N,5], iris ellipses [N,5] (pixels)."""
+    Returns edge maps [N,H,W], class maps [N,H,W], pupil ellipses [N,5], iris ellipses [N,5] (pixels).  ``args``: where the seeds of
+    the searches come from (seed_of)."""
+    seed, regions = seed_of(args)
     from egne_amd.utils import calc_edge
     assert frames.dim() == 4, 'Frame must be [N,1,H,W]'
     ns = argparse.Namespace(prec=torch.float32, edge_thres=0)
@@ -134,7 +155,7 @@ def evaluate_ellseg_on_image(frames, model, edge_model, args=None):
         # own calibration pass)
         if _overflowed(edge_model):
             continue
-        res = _to_host(_seg_and_fit(frames, model)(edge))
+        res = _to_host(_seg_and_fit(frames, model, seed=seed, regions=regions)(edge))
         if not _overflowed(model):
             return res
     raise RuntimeError("non-finite activations after re-calibration: the input frames themselves are not finite")
@@ -144,12 +165,12 @@ def _overflowed(net):
     return bool(net.overflowed()) if hasattr(net, "overflowed") else False
 
 
-def _seg_and_fit(frames, model, wfit=None, then=None):
+def _seg_and_fit(frames, model, wfit=None, then=None, seed='pred', regions=None):
     """Second stage of a batch (evaluate.py:117-166): ESF-Net on the frames and their edge maps, argmax mask, both ellipses
     fitted on the device.  Returns a callable of the edge maps (egne_amd.pipeline.TwoStagePipeline runs it on its second stream).
     ``wfit`` (egne_amd.pipeline.WindowedFit): the searches go to its stream and are released in the next batch's launch window; the
     third result is then a handle (``_to_host`` waits for it); ``then(edge, mask, fit)`` is queued on the searches' stream right behind
-    them (the device-side rendering of --device_io 1)."""
+    them (the device-side rendering of --device_io 1).  ``seed`` / ``regions``: seed_of(args)."""
     dev = frames.device
     N, _, H, W = frames.shape
 
@@ -163,13 +184,14 @@ def _seg_and_fit(frames, model, wfit=None, then=None):
                         torch.zeros(N, dtype=torch.long, device=dev), 0)
             if wfit is not None:
                 e, m = edge[:, 0].clone(), model.predictions().clone()
-                return e, m, wfit.submit(model.predictions(), out[1], then=None if then is None else (lambda fit: then(e, m, fit)))
-            fit = fit_ellipses_from_pred(model.predictions(), out[1])     # [N,2,5] on the device: (iris, pupil)
+                return e, m, wfit.submit(model.predictions(), out[1], then=None if then is None else (lambda fit: then(e, m, fit)),
+                                         seed=seed, regions=regions)
+            fit = _fit(model.predictions(), out[1], seed, regions)        # [N,2,5] on the device: (iris, pupil)
             return edge[:, 0].clone(), model.predictions().clone(), fit
     return run
 
 
-def graphed_runner(warmup_frames, model, edge_model):
+def graphed_runner(warmup_frames, model, edge_model, seed='pred', regions=None):
     """edge -> seg -> fit of a fixed small batch as one hipGraph replay (egne_amd.pipeline.GraphedFrames): the per-eye loop of
     evaluate.py:235-249 at one or two frames per call.  ``runner(frames)`` returns the same device tensors as the eager path (edge maps
     [N,H,W], class maps [N,H,W], fitted ellipses [N,2,5]); results are bit-identical to it."""
@@ -178,11 +200,11 @@ def graphed_runner(warmup_frames, model, edge_model):
     ns = argparse.Namespace(prec=torch.float32, edge_thres=0)
 
     def stage(x):
-        return _seg_and_fit(x, model)(calc_edge(ns, x, edge_model, x.device))
+        return _seg_and_fit(x, model, seed=seed, regions=regions)(calc_edge(ns, x, edge_model, x.device))
     return GraphedFrames(stage, warmup_frames)
 
 
-def graphed_runner_io(warmup_u8, model, edge_model, op_shape=(240, 320), eyes=2, eye_width=320):
+def graphed_runner_io(warmup_u8, model, edge_model, op_shape=(240, 320), eyes=2, eye_width=320, seed='pred', regions=None):
     """graphed_runner with the device front and back end INSIDE the captured graph: uint8 frames [N,Hs,Ws] in, (overlay, edge frame,
     ellipses at source geometry) out -- prep, edge, seg, fit and rendering are one replay.  Capture allows it: shapes are fixed, the
     tap tables are uploaded by the eager warm-up runs, nothing in the two stages synchronises."""
@@ -192,12 +214,12 @@ def graphed_runner_io(warmup_u8, model, edge_model, op_shape=(240, 320), eyes=2,
 
     def stage(fu):
         x, ss = preprocess_frames_device(fu, op_shape, eyes, eye_width)
-        edge, seg, fit = _seg_and_fit(x, model)(calc_edge(ns, x, edge_model, x.device))
+        edge, seg, fit = _seg_and_fit(x, model, seed=seed, regions=regions)(calc_edge(ns, x, edge_model, x.device))
         return render_frames_device(fu, edge, seg, fit, ss, eyes, eye_width)
     return GraphedFrames(stage, warmup_u8)
 
 
-def evaluate_frames_device_io(frames_u8, model, edge_model, op_shape=(240, 320), eyes=2, eye_width=320):
+def evaluate_frames_device_io(frames_u8, model, edge_model, op_shape=(240, 320), eyes=2, eye_width=320, seed='pred', regions=None):
     """evaluate_ellseg_on_image from uint8 device frames to rendered device frames (eager; the redo path of --device_io 1): the same
     re-calibration retries, nothing crosses to the host but the plans' overflow words."""
     from egne_amd.utils import calc_edge
@@ -208,7 +230,7 @@ def evaluate_frames_device_io(frames_u8, model, edge_model, op_shape=(240, 320),
             edge = calc_edge(ns, x, edge_model, x.device)
         if _overflowed(edge_model):
             continue
-        e, m, fit = _seg_and_fit(x, model)(edge)
+        e, m, fit = _seg_and_fit(x, model, seed=seed, regions=regions)(edge)
         if not _overflowed(model):
             return render_frames_device(frames_u8, e, m, fit, ss, eyes, eye_width)
     raise RuntimeError("non-finite activations after re-calibration: the input frames themselves are not finite")
@@ -893,6 +915,7 @@ def evaluate_ellseg_per_video(path_vid, args, model, edge_model, device):
     if dd and not io:
         sys.exit('evaluate.py: --device_decode 1 needs --device_io 1')
     runner = [None]
+    seed, regions = seed_of(args)                   # --ellipse_seed mask: every path below seeds the searches from the class map
 
     def flush():
         if not pending:
@@ -905,11 +928,11 @@ def evaluate_ellseg_per_video(path_vid, args, model, edge_model, device):
             # one hipGraph replay per frame pair (egne_amd.pipeline.GraphedFrames, captured on the first frame): no batching, no
             # pipelining across frames -- 4.3-4.7 ms per call on MI355X instead of a batch of 32 every ~20 ms
             if runner[0] is None or tuple(runner[0].x.shape) != tuple(x.shape):
-                runner[0] = graphed_runner(x, model, edge_model)
+                runner[0] = graphed_runner(x, model, edge_model, seed, regions)
             res = [t.clone() for t in runner[0](x)]
             if _overflowed(model) | _overflowed(edge_model):
                 # beyond the head-room of the scales baked into the captured launches: capture again (its eager warm-up runs re-calibrate)
-                runner[0] = graphed_runner(x, model, edge_model)
+                runner[0] = graphed_runner(x, model, edge_model, seed, regions)
                 res = [t.clone() for t in runner[0](x)]
                 if _overflowed(model) | _overflowed(edge_model):
                     raise RuntimeError("non-finite activations after re-calibration: the input frames themselves are not finite")
@@ -921,7 +944,7 @@ def evaluate_ellseg_per_video(path_vid, args, model, edge_model, device):
             return
         queued.append(list(pending))
         pending.clear()
-        r = pipe.submit(x, _seg_and_fit(x, model, wfit))
+        r = pipe.submit(x, _seg_and_fit(x, model, wfit, seed=seed, regions=regions))
         if r is not None:
             ready.append((queued.pop(0), r))
         while len(ready) > 1:
@@ -958,12 +981,12 @@ def evaluate_ellseg_per_video(path_vid, args, model, edge_model, device):
             if runner[0] is None or tuple(runner[0].x.shape) != tuple(batch.fu.shape):
                 if dd:
                     fix_flagged(batch)
-                runner[0] = graphed_runner_io(batch.fu, model, edge_model, (240, 320), 2, ew)
+                runner[0] = graphed_runner_io(batch.fu, model, edge_model, (240, 320), 2, ew, seed, regions)
             res = runner[0](batch.fu)
             if _overflowed(model) | _overflowed(edge_model):
                 if dd:
                     fix_flagged(batch)
-                runner[0] = graphed_runner_io(batch.fu, model, edge_model, (240, 320), 2, ew)
+                runner[0] = graphed_runner_io(batch.fu, model, edge_model, (240, 320), 2, ew, seed, regions)
                 res = runner[0](batch.fu)
                 if _overflowed(model) | _overflowed(edge_model):
                     raise RuntimeError("non-finite activations after re-calibration: the input frames themselves are not finite")
@@ -981,7 +1004,7 @@ def evaluate_ellseg_per_video(path_vid, args, model, edge_model, device):
             if dj:
                 _encode_rendered(batch)
         queued.append(batch)
-        r = pipe.submit(x, _seg_and_fit(x, model, wfit, then))
+        r = pipe.submit(x, _seg_and_fit(x, model, wfit, then, seed, regions))
         if r is not None:
             ready.append((queued.pop(0), r))
         while len(ready) > 1:
@@ -1002,7 +1025,7 @@ def evaluate_ellseg_per_video(path_vid, args, model, edge_model, device):
         if again:
             # as draw(): this batch and the one queued behind it again, from the retained uint8 device frames, rendered again
             torch.cuda.synchronize()
-            batch.rendered = evaluate_frames_device_io(batch.fu, model, edge_model, (240, 320), 2, ew)
+            batch.rendered = evaluate_frames_device_io(batch.fu, model, edge_model, (240, 320), 2, ew, seed, regions)
             if dj:
                 _encode_rendered(batch)
         if dj:
@@ -1056,7 +1079,7 @@ def evaluate_ellseg_per_video(path_vid, args, model, edge_model, device):
             redo[0] = not redo[0]
             torch.cuda.synchronize()    # the edge network of the NEXT batch is in flight on the pipeline's stream and owns the same plan buffers
             x = torch.stack([e[0] for _, _, fe in frames_of_batch for e in fe]).to(device)
-            edge, seg, pup, iri = evaluate_ellseg_on_image(x, model, edge_model)
+            edge, seg, pup, iri = evaluate_ellseg_on_image(x, model, edge_model, args)
         k = 0
         for j, frame_bgr, fe in frames_of_batch:
             overlay, edge_frame = frame_bgr.copy(), frame_bgr.copy()
@@ -1158,7 +1181,7 @@ def main(argv=None):
     if args.synthetic:
         from egne_amd import synth
         x = synth.make_batch(args.synthetic, seed=5)['img'].to(device)
-        edge, seg, pup, iri = evaluate_ellseg_on_image(x, model, edge_net)
+        edge, seg, pup, iri = evaluate_ellseg_on_image(x, model, edge_net, args)
         print('pupil ellipses:\n', pup, '\niris ellipses:\n', iri)
         return pup, iri
     res = None

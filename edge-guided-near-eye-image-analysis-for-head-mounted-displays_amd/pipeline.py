@@ -81,7 +81,8 @@ class WindowedFit:
     hand a workgroup to whichever CU is free: next to them a search costs its share of the CUs and nothing more.  Measured on
     MI355X, B = 64, edge + seg + fit pipelined (scratch/ab_fit.sh): 1998-2001 frames/s released at once, 2009-2021 in a window.
 
-    ``submit(mask, elPred, then=None)`` is called on the stream that produced the two tensors; it returns a handle: ``result`` (device
+    ``submit(mask, elPred, then=None, seed="pred", regions=None)`` is called on the stream that produced the two tensors (``seed="mask"``:
+    the seeds come from the class map, utils.fit_ellipses_from_mask with ``regions``, and elPred is not read); it returns a handle: ``result`` (device
     tensor [F,2,5], valid once the handle is done), ``synchronize()`` (host waits; queues the searches at once if their window has not
     opened yet -- the last batches of a run), ``wait(stream)``.  ``then(result)`` runs on the search stream right behind the searches
     (e.g. the copy to pinned host memory)."""
@@ -128,9 +129,11 @@ class WindowedFit:
         except Exception:
             pass
 
-    def submit(self, mask, elPred, then=None):
+    def submit(self, mask, elPred, then=None, seed="pred", regions=None):
         from . import engine
-        from .utils import fit_ellipses_from_pred
+        from .utils import fit_ellipses_from_mask, fit_ellipses_from_pred
+        if seed not in ("pred", "mask"):
+            raise ValueError("WindowedFit.submit: seed %r (pred or mask)" % (seed,))
         ready = torch.cuda.Event()
         ready.record()
         h = WindowedFit.Handle()
@@ -142,8 +145,11 @@ class WindowedFit:
                 side.wait_event(window)
             with torch.cuda.stream(side), torch.no_grad():
                 mask.record_stream(side)
-                elPred.record_stream(side)
-                h.result = fit_ellipses_from_pred(mask, elPred)
+                if seed == "mask":
+                    h.result = fit_ellipses_from_mask(mask, regions)
+                else:
+                    elPred.record_stream(side)
+                    h.result = fit_ellipses_from_pred(mask, elPred)
                 if then is not None:
                     then(h.result)
                 h.done = torch.cuda.Event()

@@ -279,6 +279,88 @@ def fit_ellipses_from_pred(mask, elPred, out=None):
     return out
 
 
+DEFAULT_SEED_REGIONS = ((0b110, 1), (0b100, 2))     # iris = classes 1 and 2 together, searched against class 1 as today; pupil = class 2
+_region_cache = {}
+
+
+def _region_rows(regions, F, dev):
+    """frame_of / class_bits / search_cls [R*F] int32 on the device for ``regions`` repeated over F frames (row R*f + r).  Cached:
+    the upload happens on the first (eager) call, so a captured graph only reads the tables."""
+    regions = tuple((int(b), int(c)) for b, c in regions)
+    if not regions:
+        raise ValueError("regions: at least one (class_bits, search_cls) pair")
+    for b, c in regions:
+        if not 0 <= b < 1 << 32:
+            raise ValueError("regions: class_bits %r is not a bitmask over class ids 0..31" % (b,))
+    key = (regions, int(F), str(dev))
+    if key not in _region_cache:
+        R = len(regions)
+        fo = np.repeat(np.arange(F, dtype=np.int32), R)
+        cb = np.tile(np.array([b for b, _ in regions], dtype=np.uint32).view(np.int32), F)
+        sc = np.tile(np.array([c for _, c in regions], dtype=np.int32), F)
+        _region_cache[key] = tuple(torch.from_numpy(a).to(dev) for a in (fo, cb, sc))
+    return _region_cache[key]
+
+
+def ellipse_seeds_from_mask(mask, regions=DEFAULT_SEED_REGIONS, min_area=7, return_stats=False):
+    """Seeds of the search from the class map itself (csrc/mask_seed.hip; not in the reference): per (frame, region) the largest
+    8-connected component of the region and the ellipse of its second moments.
+
+    mask [F,H,W] int64 class maps on the GPU; ``regions`` lists (class_bits, search_cls) per frame in output order -- a pixel belongs
+    to the region iff bit mask[p] of class_bits is set; search_cls is the class the search scores against (None: the default).  Returns (init [R*F,5]
+    float64, frame_of [R*F] int32, cls [R*F] int32) on the device, like ellipse_seeds_from_pred; row R*f + r is region r of frame f.
+    An absent region (no pixel, or fewer than ``min_area`` -- ElliFit's "more than 6 points") has init = -1 five times and frame_of =
+    -1.  With ``return_stats`` also stats int64 [R*F,8] = (N, Sx, Sy, Sxx, Sxy, Syy, components, region pixels) and the int32 status
+    word (0 = every loop ended inside its bound).  Nothing here synchronises."""
+    require_cuda(mask, "mask")
+    if mask.dtype != torch.int64 or mask.dim() != 3:
+        raise ValueError("mask must be an int64 [F,H,W] tensor")
+    L = _lib.lib()
+    dev = mask.device
+    F, H, W = (int(v) for v in mask.shape)
+    fo_in, cb, sc = _region_rows(DEFAULT_SEED_REGIONS if regions is None else regions, F, dev)
+    return _seeds_from_mask_rows(L, mask.contiguous(), fo_in, cb, sc, int(min_area), return_stats)
+
+
+def _seeds_from_mask_rows(L, m, fo_in, cb, sc, min_area, return_stats):
+    dev = m.device
+    F, H, W = (int(v) for v in m.shape)
+    n = int(fo_in.shape[0])
+    nbytes = int(L.egne_mask_seed_workspace_bytes(n, H, W))
+    if nbytes < 0:
+        raise ValueError("ellipse_seeds_from_mask: %d rows of %dx%d class maps (2..1024 rows and columns, at most 2^20 pixels)" % (n, H, W))
+    ws = torch.empty((nbytes + 7) // 8, dtype=torch.int64, device=dev)
+    init = torch.empty((n, 5), dtype=torch.float64, device=dev)
+    fo = torch.empty((n,), dtype=torch.int32, device=dev)
+    cl = torch.empty((n,), dtype=torch.int32, device=dev)
+    stats = torch.empty((n, 8), dtype=torch.int64, device=dev)
+    status = torch.empty((1,), dtype=torch.int32, device=dev)
+    _lib.check(L.egne_ellipse_init_from_mask(m.data_ptr(), F, fo_in.data_ptr(), cb.data_ptr(), sc.data_ptr(), n, H, W, min_area,
+                                             init.data_ptr(), fo.data_ptr(), cl.data_ptr(), stats.data_ptr(), status.data_ptr(),
+                                             ws.data_ptr(), _lib.stream_ptr()), "ellipse_init_from_mask")
+    return (init, fo, cl, stats, status) if return_stats else (init, fo, cl)
+
+
+def fit_ellipses_from_mask(mask, regions=DEFAULT_SEED_REGIONS, min_area=7, out=None):
+    """fit_ellipses_from_pred with the seeds of ellipse_seeds_from_mask: seeds, then every search in one launch on the same stream.
+    Returns a DEVICE tensor [F,R,5] float64, region order as in ``regions`` (default: iris, pupil); absent rows are -1 five times
+    (the search reports NaN for them; a device-side select puts the seed's -1 back).  Nothing here synchronises."""
+    init, fo, cl = ellipse_seeds_from_mask(mask, regions, min_area)
+    L = _lib.lib()
+    F, H, W = mask.shape
+    R = init.shape[0] // F
+    res = torch.empty((F * R, 5), dtype=torch.float64, device=mask.device)
+    xs, ys = _mesh_axes(H, W, mask.device)
+    m = mask.contiguous()
+    _lib.check(L.egne_ellipse_fit(m.data_ptr(), F, fo.data_ptr(), cl.data_ptr(), F * R, H, W, xs.data_ptr(), ys.data_ptr(),
+                                  init.data_ptr(), res.data_ptr(), None, _lib.stream_ptr()), "ellipse_fit")
+    sel = torch.where((fo < 0)[:, None], init, res).view(F, R, 5)
+    if out is None:
+        return sel
+    out.copy_(sel)
+    return out
+
+
 def search_proper_parameter_iou_for_our_data(seg, ell_para):
     """utils.py:450-486, same signature: seg [H,W] bool tensor on the GPU, ell_para (5,) pixels."""
     require_cuda(seg, "seg")

@@ -687,6 +687,28 @@ int egne_ellipse_iou_counts(const int64_t* mask, int nframes, const int32_t* fra
                             int H, int W, const float* xs, const float* ys, const double* ell, uint32_t* counts,
                             int roww, void* stream);
 
+/*
+ * Ellipse seeds from the class map (evaluate.py --ellipse_seed mask; csrc/mask_seed.hip; not in the reference): the seed of the
+ * search above from the segmentation itself instead of the regression head.  mask [nframes][H][W] int64 class ids; row i < n
+ * names a frame (frame_of[i]), a region (class_bits[i]: a pixel belongs iff bit mask[p] is set, ids outside 0..31 never belong)
+ * and the class the search is to score against (search_cls[i]).  Per row: label the 8-connected components of the region
+ * (multi-launch union-find, the launch boundary is the only synchronisation), choose the one with the most pixels (tie: the one
+ * whose first pixel in raster order comes first), accumulate N, Sx, Sy, Sxx, Sxy, Syy over it (x = column, y = row; 64-bit integer
+ * adds only, so order-independent) and finalise in float64 (unit-pixel term N*N/12, axes scaled by W/(W-1), H/(H-1): the
+ * search's mesh is linspace(-1,1,W) while its pixel map is 2p/W - 1): init [n][5] = (cx, cy, a, b, theta), a the semi-axis along
+ * theta.  out_frame_of[i] = frame_of[i], out_cls[i] = search_cls[i], stats [n][8] int64 = (N, Sx, Sy, Sxx, Sxy, Syy, number of
+ * components, pixels in the region).  Absent region (class_bits 0, no pixel, N < min_area, frame_of outside [0, nframes)): init
+ * -1 five times, out_frame_of -1 (egne_ellipse_fit reads nothing for it), zeros for the six sums.  Every find / union loop stops
+ * after 4*H*W + 64 steps: such a row sets bit 0 of the device word `status` (zeroed by the call) and is reported absent.
+ * Refused (nothing written): H < 2, W < 2, max(H, W) > 1024, H*W > 2^20.  ws: egne_mask_seed_workspace_bytes(n, H, W) bytes
+ * (-1 for a refused shape), aligned to 8.  Seven launches on `stream`, fixed sequence (capturable), no host synchronisation.
+ */
+int64_t egne_mask_seed_workspace_bytes(int n, int H, int W);
+int egne_ellipse_init_from_mask(const int64_t* mask, int nframes, const int32_t* frame_of, const int32_t* class_bits,
+                                const int32_t* search_cls, int n, int H, int W, int min_area, double* init,
+                                int32_t* out_frame_of, int32_t* out_cls, int64_t* stats, int32_t* status, void* ws,
+                                void* stream);
+
 /* Device-side batch preparation (the reference does this per sample on the host in its Dataset).
  * egne_dist_maps: out[b][c] = helperfunctions.one_hot2dist(label[b] == c) (helperfunctions.py:356-371, called from
  *   CurriculumLib.py:131-136): signed exact Euclidean distance transform normalised by the image diagonal, 0 for an absent
