@@ -179,6 +179,10 @@ bool msdil1_wanted(const egne_conv_desc& d);      // msblock_dil1_f16.hip: plain
 int msdil1_launch(const egne_conv_desc& d, const void* fhi, float a_scale, float w_scale, const float* score_w, const float* score_c,
                   float* s0, float* s1, int accumulate, hipStream_t st);
 
+bool msdil3_wanted(const egne_conv_desc& d);      // msblock_dil3_f16.hip: three products, ring of phase-plane rows
+int msdil3_launch(const egne_conv_desc& d, const void* fhi, const void* flo, float a_scale, float w_scale, const float* score_w,
+                  const float* score_c, float* s0, float* s1, int accumulate, hipStream_t st);
+
 inline int cdiv(long long a, long long b) { return (int)((a + b - 1) / b); }
 
 }  // namespace egne
