@@ -1,4 +1,4 @@
-// Which convolution entry point serves a layer: the C side of engine.Plan._conv_impl / _conv_bf16 (round 6).
+// Which convolution entry point serves a layer: the C side of the planner's chooser, engine.choose_conv (round 6).
 //
 // The reference has no dispatch of its own -- F.conv2d picks a backend kernel inside ATen (models/RITnet_v2.py:57-62,85-87,
 // bdcn_new.py:49-55, vgg16_c.py:65-88 all end there).  A maintainer who binds include/egne_hip.h directly
@@ -6,7 +6,7 @@
 // answers it from a layer description: the same predicates, in the same order, with the DEFAULT thresholds of engine.py (its
 // environment switches are experiment knobs of the Python planner, not part of this contract).  The planner checks itself against this
 // function for every convolution it plans when EGNE_CHECK_DISPATCH=1 (tests/test_gpu_nets.py: the B = 64 and B = 2 plans of both
-// networks, the training plans in both storages).
+// networks, the training plans in both storages); tests/test_host_dispatch.py compares the two choosers on the CPU, query by query.
 //
 // What it does NOT decide: fusing a 1x1 into the 3x3 that consumes it (egne_conv1x1_3x3_fused_f16_fwd, egne_conv3x3c4_3x3_fused_f16_fwd,
 // egne_conv1x1_pool_f16x3_fwd) is a decision about PAIRS of layers, taken by the plan builder (esf_engine.py) before either layer reaches
@@ -55,7 +55,7 @@ extern "C" int egne_conv2d_auto_kind(const egne_conv_query* qp, egne_conv_choice
   const long long st0 = q.seg_pix_stride[0];
   const int cstore = Cout_store < q.dst_Cp ? Cout_store : q.dst_Cp;
 
-  // ---------------------------------------------------------------------------------- plans with bf16 activation storage (_conv_bf16)
+  // ---------------------------------------------------------------------------------- plans with bf16 activation storage
   if (q.dtype == 1) {
     const bool one = q.nseg == 1 && q.stride == 1 && q.pad_mode == 0 && d0 == 1 && k3 && same1 && G == 1;
     const bool smallcin = one && Cin <= 4 && pad8i(Cout) <= 64 && raw && !q.has_residual && !q.is_dgrad && !q.has_post;
@@ -79,7 +79,7 @@ extern "C" int egne_conv2d_auto_kind(const egne_conv_query* qp, egne_conv_choice
     return set_kind(out, EGNE_KIND_IGEMM, "conv_igemm");
   }
 
-  // ---------------------------------------------------------------------------------- fp32 tensors (_conv_impl)
+  // ---------------------------------------------------------------------------------- fp32 tensors
   // <= 4 output channels over a narrow raw slice: exact fp32 on the vector ALU
   if (!q.train && !q.dyn_scales && k3 && q.stride == 1 && G == 1 && same1 && q.pad_mode == 0 && d0 == 1 && Cout <= 4 && q.nseg == 1 && !q.seg_planar &&
       raw && !q.seg_presplit && Cp0 >= 32 && Cp0 <= 64 && !q.has_residual && !q.want_stats && !q.want_scores && !q.want_pool &&
@@ -90,7 +90,8 @@ extern "C" int egne_conv2d_auto_kind(const egne_conv_query* qp, egne_conv_choice
               (long long)H * W * st0 < (1ll << 31);
   bool smallcin = k3 && q.stride == 1 && G == 1 && same1 && q.pad_mode == 0 && q.nseg == 1 && d0 == 1 && Cin <= 4 && pad8i(Cout) <= 64 && raw &&
                   !q.has_residual && !q.is_dgrad;
-  const bool c4h = smallcin && (q.split || q.split_c4) && pad8i(Cout) > 32;          // C4H_MODE "wide"
+  // C4H_MODE "wide"; not with device-side pre-scales (the streaming first-layer kernel reads no egne_conv_desc.dyn_scale)
+  const bool c4h = smallcin && !q.dyn_scales && (q.split || q.split_c4) && pad8i(Cout) > 32;
   // (the split-f16 flat / small / big kernels keep a row's in-range taps in a 32-bit mask: a 7x7 falls through to conv_igemm)
   bool split = q.split && q.stride == 1 && q.pad_mode == 0 && q.nseg == 1 && Cp0 >= 32 && q.kh * q.kw <= 32;
   bool shalo = split && k3 && G == 1 && same1 && d0 <= 2 && W >= (CoutP > 64 ? HALO_F16_MIN_W : HALO_F16_MIN_W_NARROW) && CoutP <= HALO_F16_MAX_COUTP &&

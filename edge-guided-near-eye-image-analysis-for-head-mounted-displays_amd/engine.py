@@ -5,7 +5,9 @@ PyTorch is used for device memory and streams only.  A *plan* is built once per
 prepared C-ABI calls (ctypes descriptors with raw device pointers), so running the network is a
 loop of ``fn(desc, stream)`` calls with no tensor allocation, no torch.cat and no host sync.
 """
+import collections
 import ctypes as C
+import types
 
 import torch
 
@@ -656,6 +658,240 @@ class BfDgradLayer(ConvLayer):
         return True
 
 
+# What ``choose_conv`` decided.  ``kind``: the string the launch carries in Plan.meta; ``rs``: a role-split form (producer / consumer waves),
+# ``rw_wide`` its streamed-weights variant; ``big1``: the plain-f16 deep trunk kernel; ``tail_frames``: frames the flat kernel takes behind
+# the deep trunk kernel; ``fused_pool`` / ``fused_stats``: what the epilogue takes along; ``small_ws``: workspace floats of the small-problem
+# form (-1: not that form); ``halo_wide96``: the halo kernel's 96-wide tile; ``c4h``: the streaming first-layer kernel
+Choice = collections.namedtuple("Choice", "kind rs rw_wide big1 tail_frames fused_pool fused_stats small_ws halo_wide96 c4h",
+                                defaults=(False, False, False, 0, False, False, -1, False, False))
+
+
+def choose_conv(q, L):
+    """Which forward entry point serves the convolution described by ``q`` (a _lib.ConvQuery, Plan._conv_query): the planner's decision,
+    as a function without side effects -- no Plan, layer or launch is touched, ``L`` answers the two host-only sizing questions.  Every
+    switch is read from this module when the function is called.  csrc/dispatch.hip (egne_conv2d_auto_kind) restates these predicates,
+    in this order, with the default switches; tests/test_host_dispatch.py holds the two against each other."""
+    B, H, W, G, nseg, d0 = q.B, q.H, q.W, q.ngroups, q.nseg, q.dil[0]
+    dils = tuple(q.dil[:G])
+    k3, k1, same1 = q.kh == 3 and q.kw == 3, q.kh == 1 and q.kw == 1, q.pad_h == 1 and q.pad_w == 1
+    Ho, Wo = (H + 2 * q.pad_h * d0 - d0 * (q.kh - 1) - 1) // q.stride + 1, (W + 2 * q.pad_w * d0 - d0 * (q.kw - 1) - 1) // q.stride + 1
+    Cin, Ktot = sum(q.seg_C[:nseg]), sum(q.seg_Cp[:nseg])
+    raw, raw0 = not any(q.seg_affine[:nseg]), not q.seg_affine[0]
+    Cout, CoutP, Cp0, st0 = q.Cout, pad32(q.Cout), q.seg_Cp[0], q.seg_pix_stride[0]
+    cstore = min(q.Cout_store, q.dst_Cp)
+    act3 = q.act in (ACT_NONE, ACT_RELU, ACT_LEAKY)
+    if q.dtype == 1:
+        # ---- bf16 activation storage: bf16-MFMA 3x3 / streaming 1x1, first layers on the taps-in-K kernel, the rest on the implicit GEMM
+        # (the planner refuses grouped convolutions here, Plan._conv_bf16; a query that describes one gets the implicit GEMM, as on the C side)
+        one = G == 1 and nseg == 1 and q.stride == 1 and q.pad_mode == 0 and d0 == 1 and k3 and same1
+        smallcin = (one and SMALLCIN_ENABLED and Cin <= 4 and pad8(Cout) <= 64 and raw0 and not q.has_residual
+                    and not q.is_dgrad and not q.has_post)
+        fast3 = (one and not smallcin and BF16_FAST3X3 and not q.has_post and Cp0 % 8 == 0 and q.seg_ch_off[0] % 8 == 0 and st0 % 8 == 0
+                 and CoutP <= 256 and cstore % 4 == 0 and cstore >= 8
+                 and H * W * max(st0, q.dst_pix_stride) < 2 ** 30
+                 and (not q.has_residual or H * W * q.res_pix_stride < 2 ** 30))
+        # 1x1 over raw slices: streaming bf16-MFMA kernel (conv1x1_bf16.hip); its weights must fit LDS (k-steps x blocks x 1 KB)
+        fast1 = (BF16_FAST1X1 and G == 1 and k1 and q.stride == 1 and q.pad_h == 0 and q.pad_w == 0 and not q.has_post
+                 and all(not q.seg_affine[i] and q.seg_Cp[i] % 8 == 0 and q.seg_ch_off[i] % 8 == 0 and q.seg_pix_stride[i] % 8 == 0 for i in range(nseg))
+                 and B * H * W >= 4096 and cstore % 8 == 0 and q.dst_ch_off % 8 == 0 and q.dst_pix_stride % 8 == 0
+                 and (not q.has_residual or (q.res_ch_off % 8 == 0 and q.res_pix_stride % 8 == 0)))
+        if fast1:
+            dq = _lib.ConvDesc()
+            dq.nseg, dq.CoutP, dq.Ktot = nseg, CoutP, Ktot
+            for i in range(nseg):
+                dq.seg[i].Cp = q.seg_Cp[i]
+            fast1 = int(L.egne_conv1x1_bf16_pack_elems(C.byref(dq))) > 0
+        if smallcin:
+            return Choice("conv3x3_smallcin")
+        if fast3:       # (statistics from its epilogue are Plan._conv_bf16's business: they also serve a caller's BatchNorm partials)
+            return Choice("conv_bf16:3x3")
+        if fast1:
+            return Choice("conv_bf16:1x1")
+        # k x k onto <= 8 channels (the data gradient of the StyleEncoder's 7x7): LDS-halo kernel instead of 98 implicit-GEMM steps
+        if q.narrow_bf16_ok:
+            return Choice("conv_bf16:narrow")
+        return Choice("conv_igemm")
+    # ---- fp32 tensors
+    # <= 4 output channels over a narrow raw slice (ESF-Net's logits layer, 32 -> 3 at full resolution): exact fp32 on the vector
+    # ALU, weights as scalar operands (conv_narrow_f32.hip) -- the matrix kernels compute a 32-wide output block for it
+    if (NARROW_F32 and not q.train and not q.dyn_scales and k3 and q.stride == 1 and G == 1
+            and same1 and q.pad_mode == 0 and d0 == 1 and Cout <= 4 and nseg == 1
+            and not q.seg_planar and raw0 and q.seg_presplit != 1
+            and 32 <= Cp0 <= 64 and not q.has_residual and not q.want_stats and not q.want_scores
+            and not q.want_pool and act3
+            and H * W * st0 < 2 ** 29):
+        return Choice("conv3x3_narrow")
+    halo = (HALO_ENABLED and k3 and q.stride == 1 and G == 1
+            and same1 and q.pad_mode == 0 and nseg == 1 and d0 <= 2
+            and W >= HALO_MIN_W and CoutP <= HALO_MAX_COUTP and H * W * st0 < 2 ** 31)
+    smallcin = (SMALLCIN_ENABLED and k3 and q.stride == 1 and G == 1
+                and same1 and q.pad_mode == 0 and nseg == 1 and d0 == 1
+                and Cin <= 4 and pad8(Cout) <= 64 and raw0 and not q.has_residual
+                and not q.is_dgrad)      # (a first-writer data gradient has no residual either)
+    # frozen nets: streaming split-f16 form (both forms run at the HBM write rate; measured 12 % faster for 64 output
+    # channels, 7 % slower for 32)
+    c4h = (smallcin and F16X3_ENABLED and (q.split or q.split_c4)
+           and (C4H_MODE == "all" or (C4H_MODE == "wide" and pad8(Cout) > 32)))
+    # (the split-f16 flat / small / big kernels keep a row's in-range taps in a 32-bit mask: a 7x7 falls through to conv_igemm)
+    split = (F16X3_ENABLED and q.split and q.stride == 1 and q.pad_mode == 0 and nseg == 1
+             and Cp0 >= 32 and q.kh * q.kw <= 32)
+    # narrow 3x3 layers on wide images: split-f16 arithmetic AND the LDS halo (input fetched once for 9 taps)
+    shalo = (split and HALO_F16_ENABLED and k3 and G == 1 and same1
+             and d0 <= 2 and W >= (HALO_F16_MIN_W if CoutP > 64 else HALO_F16_MIN_W_NARROW)
+             and CoutP <= HALO_F16_MAX_COUTP and not q.has_residual
+             and H * W * st0 < 2 ** 31)
+    # fused dilated group of an MSBlock: three lattice-halo launches (out = o + sum_g relu(conv_g(o)))
+    lattice = (split and LATTICE_ENABLED and G == 3 and k3 and same1
+               and CoutP in (32, 64) and q.has_residual and raw0
+               and min(W // d_ for d_ in dils) >= LATTICE_MIN_W and H * W * st0 < 2 ** 31)
+    # 1x1 over raw slices: streaming split-f16 kernel (weights in LDS, operands straight from HBM: conv1x1_f16.hip); its weight image
+    # and, with an up-sampled addend, the addend patch of each wave must fit 80 KB of LDS
+    s1x1 = (not q.has_residual and F16X3_ENABLED and S1X1_ENABLED and not q.dyn_scales and q.split1 and k1
+            and q.stride == 1 and G == 1 and q.pad_h == 0 and q.pad_w == 0 and not q.has_post
+            and raw and (CoutP == 32 or CoutP % 64 == 0)
+            and sum((q.seg_Cp[i] + 15) // 16 for i in range(nseg)) * (1 if CoutP == 32 else 2) * 2048
+            + (4 * 18 * (32 * (1 if CoutP == 32 else 2) + 8) * 4 if q.up_add else 0) <= 80 * 1024
+            and B * H * W >= S1X1_MIN_PIX)
+    # 1x1 over raw slices that the streaming kernel cannot take (K or Cout too large): LDS-staged split-f16 GEMM
+    ms1x1 = (F16X3_ENABLED and MS1X1_ENABLED and not s1x1 and q.split1 and k1 and q.stride == 1
+             and G == 1 and q.pad_h == 0 and q.pad_w == 0 and not q.has_residual and not q.has_post
+             and raw and Cout > 32 and B * H * W >= MS1X1_MIN_PIX)
+    # wide trunk layers: deep 256-wide split-f16 kernel (weights by LDS-DMA, one barrier per K step)
+    big = (split and BIG_ENABLED and G == 1 and raw0 and Cp0 % 32 == 0 and not q.has_residual
+           and not q.has_post and Cout % 128 == 0 and Cout >= BIG_MIN_COUT and Cin >= BIG_MIN_CIN
+           and B * Ho * Wo >= 256 * 128)
+    # ... or, for the standard dilations, ONE launch with the 4-way sum in registers (msblock_dil_f16.hip)
+    msdil = (split and MSDIL_ENABLED and G == 3 and k3 and same1
+             and dils == (4, 8, 12) and CoutP == 32 and Cp0 == 32 and q.has_residual
+             and raw0 and q.act == ACT_RELU and not q.has_post
+             and H * W * st0 < 2 ** 29 and H * W * q.dst_pix_stride < 2 ** 29)
+    if msdil:
+        lattice = False
+    if q.dyn_scales:     # kernels that read egne_conv_desc.dyn_scale: role-split / resident-weights / halo / flat
+        s1x1 = ms1x1 = big = lattice = msdil = c4h = False
+    # (the routing rules see the 64-multiple row count of the fragment pack; the 96-wide tile is decided once the kernel is known)
+    sfrag_coutp = CoutP if CoutP <= 64 else (CoutP + 63) // 64 * 64
+    split_coutp = (Cout + 127) // 128 * 128 if (Cout > 64 and G == 1) else CoutP
+    # narrow-input 3x3 layers on wide maps: producer / consumer waves (conv3x3_rs_f16.hip) instead of the all-in-one halo kernel
+    rs = (split and RS_ENABLED and HALO_F16_ENABLED and not lattice and not msdil and k3
+          and G == 1 and same1 and q.stride == 1 and q.pad_mode == 0 and d0 == 1
+          and nseg == 1 and W >= (RS_MIN_W_F16 if q.f16_products == 1 else RS_MIN_W) and H * W * max(st0, q.dst_pix_stride) < 2 ** 29
+          and (not q.has_residual or H * W * q.res_pix_stride < 2 ** 29))
+    # wider inputs: the resident-weights kernel with its weights streamed chunk by chunk (no statistics from its epilogue)
+    # (measured against the halo kernel: ahead for 128 -> 32 at 120x160 (290 vs 318 us), level or behind at 60x80 and for wide
+    #  outputs -- every output block stages the input again --, so only single-block layers on wide maps take it by default)
+    rw_wide = (rs and RW_ENABLED and 64 < Cp0 <= RW_MAX_CP and sfrag_coutp <= RW_MAX_COUTP and not q.want_stats
+               and W >= (RW_MIN_W_F16 if q.f16_products == 1 else RW_MIN_W) and cstore % 8 == 0 and q.dst_pix_stride % 4 == 0 and q.dst_ch_off % 4 == 0
+               and (not q.has_residual or (q.res_pix_stride % 4 == 0 and q.res_ch_off % 4 == 0)))
+    rs = rw_wide or (rs and 8 <= Cp0 <= 64 and sfrag_coutp in (32, 64, 128)
+                     and not (Cp0 <= 32 and sfrag_coutp == 128))
+    # a slice whose last 32-channel chunk holds <= 16 channels (38 -> 64 of ESF-Net's second down block): the halo kernel skips the
+    # zero half of that chunk's k-steps (3 of 4 for 40 channels), the role-split kernels' 16x16x32 MFMAs cannot
+    if rs and not rw_wide and TAIL16_HALO and 32 < Cp0 <= 64 and 0 < Cp0 % 32 <= 16:
+        rs = False
+    shalo = shalo or rs
+    if lattice or msdil:
+        shalo = True
+    if split and not shalo and halo and not raw0 and CoutP <= 32 and W >= HALO_F16_MIN_W:
+        split = False            # narrow fused-affine layers: the fp32 halo kernel beats the flat split kernel
+    if smallcin:
+        split = shalo = False
+    # small problems (one or two frames at the deep levels): 64-wide tiles + split-K on the flat kernel (conv_f16x3.hip small_plan)
+    small_ws = -1
+    if SMALL_ENABLED and split and not q.train and G == 1 and not (lattice or msdil):
+        dq = _lib.ConvDesc()
+        dq.B, dq.Ho, dq.Wo, dq.kh, dq.kw, dq.ngroups, dq.CoutP = B, Ho, Wo, q.kh, q.kw, 1, split_coutp
+        dq.seg[0].Cp = Cp0
+        small_ws = int(L.egne_conv2d_f16x3_small_workspace_floats(C.byref(dq)))
+    small = small_ws >= 0
+    tall = ((H + 31) // 32) * ((W + 7) // 8) < ((W + 31) // 32) * ((H + 7) // 8)      # conv_halo_f16.hip would walk the map transposed
+    if small and q.want_stats and STATS_FUSED and shalo and q.dst_Cp == cstore:
+        if rs or (d0 == 1 and not tall):
+            small = False            # the halo / role-split kernel writes the consumer's InstanceNorm sums from its epilogue: one launch
+    if small:
+        shalo = rs = big = False
+    if smallcin or split:
+        halo = False
+    if big:
+        big1 = BIG1_ENABLED and q.f16_products == 1 and (pad32(Ktot) // 32 * q.kh * q.kw) % 2 == 0
+        # frames handed to the 128x128 kernel so that the 256x256 launch fills whole rounds of 256 CUs
+        big_tail = 0
+        bn = 256 if Cout % 256 == 0 else 128
+        ny = (Cout + bn - 1) // bn
+        wgs = lambda nb: (nb * Ho * Wo + 255) // 256 * ny      # noqa: E731
+        full = wgs(B) // BIG_CUS
+        if BIG_SPLIT_TAIL and full >= 1 and 0.04 < wgs(B) / BIG_CUS - full < 0.65:
+            b1 = B
+            while b1 > 1 and wgs(b1) > full * BIG_CUS:
+                b1 -= 1
+            if wgs(b1) >= 0.9 * full * BIG_CUS:
+                big_tail = B - b1
+        if q.f16_storage and big1:
+            big_tail = 0                      # (the flat kernel behind a ragged last round reads and writes fp32)
+        return Choice("conv_f16x3:big", big1=big1, tail_frames=big_tail)
+    if s1x1:
+        return Choice("conv_f16x3:stream1x1")
+    if ms1x1:
+        return Choice("conv_f16x3:gemm1x1")
+    if msdil:
+        return Choice("conv_f16x3:msdil")
+    if lattice:
+        return Choice("conv_f16x3:lattice")
+    if shalo and rs:
+        pooled = bool(q.want_pool and POOL_FUSED and Cp0 > 32 and sfrag_coutp >= 64 and not q.has_post
+                      and act3 and q.pool_Cp >= cstore)
+        fuse_stats = bool(q.want_stats and STATS_FUSED and q.dst_Cp == cstore)
+        # resident-weights form (conv3x3_rw_f16.hip) unless the layer writes InstanceNorm sums from its epilogue
+        # (measured at 240x320x64 against the register-ring form: 64 -> 32 566 vs 777 us, 64 -> 64 1070 vs 1170, 32 -> 32 318 vs 356,
+        #  32 -> 64 622 vs 740; 64 -> 128 at 120x160 525 vs 560)
+        rw = rw_wide or (RW_ENABLED and not fuse_stats
+                         and cstore % 8 == 0 and q.dst_pix_stride % 4 == 0 and q.dst_ch_off % 4 == 0
+                         and (not q.has_residual or (q.res_pix_stride % 4 == 0 and q.res_ch_off % 4 == 0)))
+        return Choice("conv_f16x3:rw" if rw else "conv_f16x3:rs", rs=True, rw_wide=rw_wide, fused_pool=pooled, fused_stats=fuse_stats)
+    if shalo:
+        fuse_stats = bool(q.want_stats and STATS_FUSED and d0 == 1 and q.dst_Cp == cstore)
+        pooled = bool(q.want_pool and POOL_FUSED and HALO_POOL and not q.want_stats and d0 == 1 and not q.has_post
+                      and not q.has_residual and act3 and q.pool_Cp >= cstore and sfrag_coutp % 64 == 0
+                      and ((H + 1) // 2) * ((W + 1) // 2) * q.pool_pix_stride < 2 ** 29)      # pool2 of vgg16_c.py:72 from conv2_2's epilogue
+        # 96 outputs on the plain halo kernel (three products, dilation 1, no pooled second output): its 96-wide tile
+        wide96 = CoutP == 96 and d0 == 1 and q.f16_products != 1 and not q.want_pool
+        return Choice("conv_f16x3:halo", fused_pool=pooled, fused_stats=fuse_stats, halo_wide96=wide96)
+    if split and small:
+        return Choice("conv_f16x3:small", small_ws=small_ws)
+    if split:
+        return Choice("conv_f16x3:flat")
+    if smallcin and c4h:
+        return Choice("conv_f16x3:first", c4h=True)
+    if smallcin:
+        return Choice("conv3x3_smallcin")
+    if halo:
+        return Choice("conv3x3_halo")
+    return Choice("conv_igemm")
+
+
+# kind -> (ConvLayer.need_* flags of the packs it reads, split-f16 packs?, fragment-order f16 pack?, the Plan method that adds its launches)
+_KIND = {
+    "conv3x3_narrow": (("need_flat",), False, False, "_emit_narrow_f32"),
+    "conv_f16x3:big": (("need_big", "need_flat"), True, False, "_emit_big"),
+    "conv_f16x3:stream1x1": (("need_s1", "need_flat"), False, False, "_emit_stream1x1"),
+    "conv_f16x3:gemm1x1": (("need_m1", "need_flat"), False, False, "_emit_gemm1x1"),
+    "conv_f16x3:msdil": ((), True, True, "_emit_msdil"),
+    "conv_f16x3:lattice": ((), True, True, "_emit_lattice"),
+    "conv_f16x3:rw": ((), True, True, "_emit_rs_rw"),
+    "conv_f16x3:rs": ((), True, True, "_emit_rs_rw"),
+    "conv_f16x3:halo": ((), True, True, "_emit_halo"),
+    "conv_f16x3:small": (("need_split",), True, False, "_emit_small"),
+    "conv_f16x3:flat": (("need_split",), True, False, "_emit_flat"),
+    "conv_f16x3:first": (("need_c4h", "need_c4", "need_flat"), False, False, "_emit_first"),   # (the backward (wgrad) paths index the generic pack with kinv)
+    "conv3x3_smallcin": (("need_c4", "need_flat"), False, False, "_emit_smallcin"),
+    "conv3x3_halo": (("need_frag",), False, False, "_emit_halo_f32"),
+    "conv_igemm": (("need_flat",), False, False, "_emit_igemm"),
+    "conv_bf16:3x3": (("need_bfrag",), False, False, "_emit_bf16_3x3"),
+    "conv_bf16:1x1": (("need_flat", "need_b1"), False, False, "_emit_bf16_1x1"),
+    "conv_bf16:narrow": (("need_flat",), False, False, "_emit_bf16_narrow"),
+}
+
+
 class Plan:
     """Buffers + prepared launches for one network at one shape."""
 
@@ -695,7 +931,7 @@ class Plan:
         # behind every run, the event that says the copy has landed
         self.ovf = self.ovf_host = self.ovf_event = None
         self.overflow_events = 0
-        self._want_partials, self.last_partials = False, None      # _conv_bf16: the caller wants the statistics partials of the next 3x3 launch
+        self.last_partials = None                      # _conv_bf16: the statistics partials of a 3x3 launch whose caller asked for them (conv(partials=True))
         self._mask_cands3 = {}                         # as _mask_cands, for slices whose last writer is a bf16 3x3 data gradient (egne_conv_desc.mask_y)
         self._last_b3_desc = None
         self._premasked = {}                           # (buffer id, first channel) -> samples whose output gradient already is the masked gz, bias sums taken (esf_engine._train_bn)
@@ -1026,81 +1262,73 @@ class Plan:
                   name + ".stats", kind="norm_stats")
         return scale, shift
 
-    def msdil_ok(self, layer, piece, H, W):
-        """True if pl.conv will run this grouped dilated MSBlock convolution on the one-launch kernel (msblock_dil_f16.hip)."""
-        return (F16X3_ENABLED and layer.split and MSDIL_ENABLED and layer.G == 3 and layer.kh == 3 and layer.kw == 3
-                and layer.pad == (1, 1) and layer.dils == (4, 8, 12) and layer.CoutP == 32 and piece.Cp == 32 and piece.scale is None
-                and layer.act == ACT_RELU and layer.post is None and H * W * piece.stride < 2 ** 29)
-
-    def stream1x1_ok(self, layer, pieces, B, H, W, up_add=False):
-        """True if ``conv`` runs this 1x1 over raw slices on the streaming split-f16 kernel (weights in LDS, operands straight from
-        HBM: conv1x1_f16.hip) -- the kernel that can add an up-sampled half-resolution tensor in its epilogue (``up_add``)."""
-        return (F16X3_ENABLED and S1X1_ENABLED and not self.bf16 and not self.dyn_scales and layer.split1 and layer.kh == 1 and layer.kw == 1
-                and layer.stride == 1 and layer.G == 1 and layer.pad == (0, 0) and layer.post is None
-                and all(pc.scale is None for pc in pieces) and (layer.CoutP == 32 or layer.CoutP % 64 == 0)
-                and sum((pc.Cp + 15) // 16 for pc in pieces) * (1 if layer.CoutP == 32 else 2) * 2048
-                + (4 * 18 * (32 * (1 if layer.CoutP == 32 else 2) + 8) * 4 if up_add else 0) <= 80 * 1024       # (+ the addend patch of each wave)
-                and B * H * W >= S1X1_MIN_PIX)
-
-    def _check_dispatch(self, n0, layer, pieces, dst, B, H, W, residual, name, stats, scores, pool, up_add):
-        """EGNE_CHECK_DISPATCH=1: describe the layer to egne_conv2d_auto_kind and demand the kind this planner just recorded (the first
-        launch the convolution added to Plan.meta), the frames it handed to the flat kernel behind the deep trunk kernel and what its
-        epilogue took along."""
-        conv_kinds = [k for k, _ in self.meta[n0:] if k.startswith("conv")]
-        if not conv_kinds:
-            return
-        mine = conv_kinds[0]
+    # ---- convolutions: query -> choose_conv -> packs -> descriptor -> storage rules -> emitter -> tape -----------------------------
+    def _conv_query(self, layer, pieces, dst, B, H, W, residual=None, stats=False, scores=None, pool=None, up_add=None):
+        """The layer as choose_conv and egne_conv2d_auto_kind (csrc/dispatch.hip) see it.  ``dst`` may be None and the pieces may be
+        stand-ins without an address where a caller only asks a question that does not depend on them (stream1x1_ok)."""
         q = _lib.ConvQuery()
-        q.dtype = 1 if self.bf16 else 0
-        q.B, q.H, q.W = B, H, W
+        q.dtype, q.B, q.H, q.W = (1 if self.bf16 else 0), B, H, W
         q.kh, q.kw, q.stride, q.pad_h, q.pad_w, q.pad_mode, q.ngroups = layer.kh, layer.kw, layer.stride, layer.pad[0], layer.pad[1], layer.pad_mode, layer.G
         for g in range(_lib.MAXGROUP):
             q.dil[g] = layer.dils[g] if g < layer.G else 1
         q.nseg = len(pieces)
         for i, p in enumerate(pieces):
-            q.seg_C[i], q.seg_Cp[i], q.seg_ch_off[i], q.seg_pix_stride[i] = p.C, p.Cp, p.off, p.stride
+            q.seg_C[i], q.seg_Cp[i], q.seg_ch_off[i], q.seg_pix_stride[i] = p.C, p.Cp, getattr(p, "off", 0), getattr(p, "stride", 0)
             q.seg_affine[i] = int(p.scale is not None)
         p0 = pieces[0]
         q.seg_planar, q.seg_presplit = int(isinstance(p0, PlanarPiece)), int(getattr(p0, "presplit", None) is not None)
         if getattr(p0, "split3", None) is not None:
             q.seg_presplit = 3
         q.Cout, q.Cout_store = layer.Cout, layer.Cout_store
-        q.dst_Cp, q.dst_ch_off, q.dst_pix_stride = dst.Cp, dst.off, dst.stride
+        if dst is not None:
+            q.dst_Cp, q.dst_ch_off, q.dst_pix_stride = dst.Cp, dst.off, dst.stride
         q.act, q.has_post, q.has_residual = layer.act, int(layer.post is not None), int(residual is not None)
         if residual is not None:
             q.res_pix_stride, q.res_ch_off = residual.stride, residual.off
         q.split, q.split1, q.split_c4 = int(bool(layer.split)), int(bool(layer.split1)), int(bool(getattr(layer, "split_c4", False)))
         q.train, q.dyn_scales = int(bool(self.train)), int(bool(self.dyn_scales))
         q.is_dgrad = int(isinstance(layer, (DgradLayer, SplitDgradLayer, BfDgradLayer)))
-        q.want_stats = int(bool(stats) and STATS_FUSED)
-        q.want_scores = int(scores is not None)
-        if pool is not None and POOL_FUSED:
+        q.want_stats, q.want_scores = int(bool(stats)), int(scores is not None)      # (what the caller asks for: whether an epilogue takes it along is choose_conv's answer)
+        if pool is not None:
             q.want_pool, q.pool_Cp, q.pool_pix_stride = 1, pool.Cp, pool.stride
-        q.up_add = int(up_add is not None)
-        q.narrow_bf16_ok = int(mine == "conv_bf16:narrow")
+        q.up_add = int(bool(up_add))        # (narrow_bf16_ok: _conv_bf16 asks egne_conv_narrow_bf16_supported where the choice comes down to that kernel)
         q.f16_products = int(self.f16_products)
-        q.f16_storage = int(getattr(p0, "f16s", None) is not None or dst.f16s is not None)
+        q.f16_storage = int(getattr(p0, "f16s", None) is not None or (dst is not None and dst.f16s is not None))
+        return q
+
+    def msdil_ok(self, layer, piece, H, W):
+        """True if pl.conv will run this grouped dilated MSBlock convolution (out = piece + sum_g relu(conv_g(piece))) on the
+        one-launch kernel (msblock_dil_f16.hip)."""
+        return choose_conv(self._conv_query(layer, [piece], piece, 1, H, W, residual=piece), self.L).kind == "conv_f16x3:msdil"
+
+    def stream1x1_ok(self, layer, pieces, B, H, W, up_add=False):
+        """True if ``conv`` runs this 1x1 over raw slices on the streaming split-f16 kernel (weights in LDS, operands straight from
+        HBM: conv1x1_f16.hip) -- the kernel that can add an up-sampled half-resolution tensor in its epilogue (``up_add``)."""
+        return len(pieces) <= _lib.MAXSEG and choose_conv(self._conv_query(layer, pieces, None, B, H, W, up_add=up_add), self.L).kind == "conv_f16x3:stream1x1"
+
+    def bf16_stream1x1_ok(self, layer, pieces, dst, B, H, W):
+        """True if ``conv`` runs this 1x1 of a bf16-storage plan on the streaming bf16-MFMA kernel (conv1x1_bf16.hip) -- the one that
+        can add an up-sampled half-resolution tensor in its epilogue (``up_add``)."""
+        return len(pieces) <= _lib.MAXSEG and choose_conv(self._conv_query(layer, pieces, dst, B, H, W), self.L).kind == "conv_bf16:1x1"
+
+    def _check_dispatch(self, q, choice, name):
+        """EGNE_CHECK_DISPATCH=1: put the same query to egne_conv2d_auto_kind and demand the planner's kind, whether frames go to the
+        flat kernel behind the deep trunk kernel, and what the epilogue takes along."""
         ch = _lib.ConvChoice()
         _lib.check(self.L.egne_conv2d_auto_kind(C.byref(q), C.byref(ch)), "conv2d_auto_kind")
-        theirs = ch.name.decode()
-        DISPATCH_LOG.append((name, mine, theirs))
-        assert theirs == mine, "%s: the planner chose %s, egne_conv2d_auto_kind %s" % (name, mine, theirs)
-        if mine == "conv_f16x3:big":
-            tails = [k for k, _ in self.meta[n0:] if k == "conv_f16x3:flat"]
-            assert bool(ch.tail_frames) == bool(tails), "%s: frame tail %d against %s" % (name, ch.tail_frames, tails)
-        if mine in ("conv_f16x3:rw", "conv_f16x3:rs", "conv_f16x3:halo") and not self.bf16:
-            assert bool(ch.fused_pool) == bool(self.last_pooled), "%s: pooled output %d against %s" % (name, ch.fused_pool, self.last_pooled)
+        mine = (choice.kind, bool(choice.tail_frames), choice.fused_pool, choice.fused_stats)
+        theirs = (ch.name.decode(), bool(ch.tail_frames), bool(ch.fused_pool), bool(ch.fused_stats))
+        DISPATCH_LOG.append((name, mine[0], theirs[0]))
+        assert mine == theirs, "%s: the planner chose %s (kind, frame tail, pooled output, statistics), egne_conv2d_auto_kind %s" % (name, mine, theirs)
 
-    def conv(self, layer, pieces, dst, B, H, W, residual=None, name="conv", stats=False, scores=None, pool=None, up_add=None):
+    def conv(self, layer, pieces, dst, B, H, W, residual=None, name="conv", stats=False, scores=None, pool=None, up_add=None, partials=False):
         """``pool``: a Piece for the 2x2 / stride-2 ceil-mode max pooling of the result; ``self.last_pooled`` tells the caller
         whether the convolution kernel wrote it (otherwise the caller runs maxpool2).  ``up_add`` = (P, ph, pw): a half-resolution
-        tensor whose bilinear x2 up-sampling is added to the result of a streaming 1x1 (callers check ``stream1x1_ok`` first)."""
-        self._pool_req, self.last_pooled, self.last_presplit, self._up_add = pool, False, False, up_add
-        n0 = len(self.meta)
-        r = self._conv_impl(layer, pieces, dst, B, H, W, residual, name, stats, scores)
-        if CHECK_DISPATCH:
-            self._check_dispatch(n0, layer, pieces, dst, B, H, W, residual, name, stats, scores, pool, up_add)
-        self._pool_req = self._up_add = None
+        tensor whose bilinear x2 up-sampling is added to the result of a streaming 1x1 (callers check ``stream1x1_ok`` /
+        ``bf16_stream1x1_ok`` first).  ``partials``: the caller wants the statistics partial sums a bf16 3x3 leaves in its epilogue
+        (``self.last_partials``; a BatchNorm finishes them over its own sample range)."""
+        self.last_pooled = self.last_presplit = False
+        r = self._conv_impl(layer, pieces, dst, B, H, W, residual, name, stats, scores, pool, up_add, partials)
         # algorithmic bytes of the layer: every input slice read once, the output written once -- in the storage the plan holds them in (a plain-f16
         # plan keeps some tensors as f16: Piece.f16s; of a split-pair slice it reads and writes the hi plane only)
         def esz_of(p):
@@ -1112,196 +1340,27 @@ class Plan:
         LAYER_BYTES[name] = B * (H * W * sum(p.Cp * esz_of(p) for p in pieces) + r[0] * r[1] * (min(layer.Cout_store, dst.Cp) * esz_of(dst) + (residual.Cp * esz_of(residual) if residual is not None else 0)))
         return r
 
-    def _conv_impl(self, layer, pieces, dst, B, H, W, residual=None, name="conv", stats=False, scores=None):
-        """pieces: input Pieces in concat order; dst: output Piece.  Returns (Ho, Wo); with ``stats`` also leaves the
-        per-sample InstanceNorm (scale, shift) of the OUTPUT in ``self.last_stats`` -- from partial sums written by the
-        kernel's epilogue where the kernel can do that, from a separate statistics pass otherwise."""
-        assert len(pieces) == len(layer.in_layout) and len(pieces) <= _lib.MAXSEG, name
-        for p, (c, cp) in zip(pieces, layer.in_layout):
-            assert p.Cp == cp and p.C == c, (name, p.C, p.Cp, c, cp)
-        if self.bf16:
-            return self._conv_bf16(layer, pieces, dst, B, H, W, residual, name, stats, scores)
-        Ho, Wo = layer.out_hw(H, W)
-        # <= 4 output channels over a narrow raw slice (ESF-Net's logits layer, 32 -> 3 at full resolution): exact fp32 on the vector
-        # ALU, weights as scalar operands (conv_narrow_f32.hip) -- the matrix kernels compute a 32-wide output block for it
-        if (NARROW_F32 and not self.train and not self.dyn_scales and layer.kh == 3 and layer.kw == 3 and layer.stride == 1 and layer.G == 1
-                and layer.pad == (1, 1) and layer.pad_mode == 0 and layer.dils[0] == 1 and layer.Cout <= 4 and len(pieces) == 1
-                and not isinstance(pieces[0], PlanarPiece) and pieces[0].scale is None and pieces[0].presplit is None
-                and 32 <= pieces[0].Cp <= 64 and residual is None and not stats and scores is None
-                and getattr(self, "_pool_req", None) is None and layer.act in (ACT_NONE, ACT_RELU, ACT_LEAKY)
-                and H * W * pieces[0].stride < 2 ** 29):
-            layer.need_flat = True
-            if layer not in self.layers:
-                self.layers.append(layer)
-            layer.ensure_packed(self.device)
-            d = _lib.ConvDesc()
-            d.ovf_flag, d.f16_products = self.ovf_ptr(), self.f16_products
-            d.B, d.H, d.W, d.Ho, d.Wo = B, H, W, Ho, Wo
-            d.kh, d.kw, d.stride, d.pad_h, d.pad_w, d.pad_mode, d.ngroups = 3, 3, 1, 1, 1, 0, 1
-            for g in range(_lib.MAXGROUP):
-                d.dil[g] = 1
-            d.nseg = 1
-            p0 = pieces[0]
-            sg = d.seg[0]
-            sg.ptr, sg.pix_stride, sg.ch_off, sg.Cp, sg.act_in = p0.ptr, p0.stride, p0.off, p0.Cp, p0.act_in
-            cp32 = (p0.Cp + 31) // 32 * 32
-            wn = self.vec(9 * cp32 * 4)          # [tap][channel][4 outputs]: re-packed when the weight changes
-
-            def repack(layer=layer, wn=wn):
-                w = layer.weights[0].detach().to(torch.float32).contiguous()
-                _lib.check(self.L.egne_pack_conv3x3_narrow_weight(w.data_ptr(), layer.Cout, layer.Cin, wn.data_ptr(), _lib.stream_ptr()), "pack_conv3x3_narrow")
-            self.pre.append(VersionGuard([layer.weights[0]], repack))
-            d.Ktot, d.CoutP, d.w = cp32, 4, wn.data_ptr()
-            d.bias = layer.bp.data_ptr() if layer.biases is not None else None
-            d.act = layer.act
-            if layer.post is not None:
-                d.post_scale, d.post_shift = layer.post[0].data_ptr(), layer.post[1].data_ptr()
-            d.out, d.out_pix_stride, d.out_ch_off = dst.ptr, dst.stride, dst.off
-            # the kernel computes four outputs (two packed multiply-adds per operand: no more instructions than three) and stores the
-            # slice's padding channels as zeros, like every other convolution of the library (the pack's rows, the bias and the post
-            # affine beyond Cout are zero)
-            d.Cout_store = min(layer.Cout_store, dst.Cp)
-            assert int(self.L.egne_conv3x3_narrow_supported(C.byref(d))) == 1 and p0.act_in == ACT_NONE, name
-            self.keep.append(d)
-            self._add(self.L.egne_conv3x3_narrow_fwd, (C.byref(d),), name, flops=2.0 * B * H * W * layer.Cout * layer.Cin * 9, kind="conv3x3_narrow")
-            return Ho, Wo
-        halo = (HALO_ENABLED and layer.kh == 3 and layer.kw == 3 and layer.stride == 1 and layer.G == 1
-                and layer.pad == (1, 1) and layer.pad_mode == 0 and len(pieces) == 1 and layer.dils[0] <= 2
-                and W >= HALO_MIN_W and layer.CoutP <= HALO_MAX_COUTP and H * W * pieces[0].stride < 2 ** 31)
-        smallcin = (SMALLCIN_ENABLED and layer.kh == 3 and layer.kw == 3 and layer.stride == 1 and layer.G == 1
-                    and layer.pad == (1, 1) and layer.pad_mode == 0 and len(pieces) == 1 and layer.dils[0] == 1
-                    and layer.Cin <= 4 and pad8(layer.Cout) <= 64 and pieces[0].scale is None and residual is None
-                    and not isinstance(layer, (DgradLayer, SplitDgradLayer)))      # (a first-writer data gradient has no residual either)
-        # frozen nets: streaming split-f16 form (both forms run at the HBM write rate; measured 12 % faster for 64 output
-        # channels, 7 % slower for 32)
-        c4h = (smallcin and F16X3_ENABLED and (layer.split or getattr(layer, "split_c4", False))
-               and (C4H_MODE == "all" or (C4H_MODE == "wide" and pad8(layer.Cout) > 32)))
-        # (the split-f16 flat / small / big kernels keep a row's in-range taps in a 32-bit mask: a 7x7 falls through to conv_igemm)
-        split = (F16X3_ENABLED and layer.split and layer.stride == 1 and layer.pad_mode == 0 and len(pieces) == 1
-                 and pieces[0].Cp >= 32 and layer.kh * layer.kw <= 32)
-        # narrow 3x3 layers on wide images: split-f16 arithmetic AND the LDS halo (input fetched once for 9 taps)
-        shalo = (split and HALO_F16_ENABLED and layer.kh == 3 and layer.kw == 3 and layer.G == 1 and layer.pad == (1, 1)
-                 and layer.dils[0] <= 2 and W >= (HALO_F16_MIN_W if layer.CoutP > 64 else HALO_F16_MIN_W_NARROW)
-                 and layer.CoutP <= HALO_F16_MAX_COUTP and residual is None
-                 and H * W * pieces[0].stride < 2 ** 31)
-        # fused dilated group of an MSBlock: three lattice-halo launches (out = o + sum_g relu(conv_g(o)))
-        lattice = (split and LATTICE_ENABLED and layer.G == 3 and layer.kh == 3 and layer.kw == 3 and layer.pad == (1, 1)
-                   and layer.CoutP in (32, 64) and residual is not None and pieces[0].scale is None
-                   and min(W // d_ for d_ in layer.dils) >= LATTICE_MIN_W and H * W * pieces[0].stride < 2 ** 31)
-        # 1x1 over raw slices: streaming split-f16 kernel (weights in LDS, operands straight from HBM)
-        s1x1 = residual is None and self.stream1x1_ok(layer, pieces, B, H, W)
-        # 1x1 over raw slices that the streaming kernel cannot take (K or Cout too large): LDS-staged split-f16 GEMM
-        ms1x1 = (F16X3_ENABLED and MS1X1_ENABLED and not s1x1 and layer.split1 and layer.kh == 1 and layer.kw == 1 and layer.stride == 1
-                 and layer.G == 1 and layer.pad == (0, 0) and residual is None and layer.post is None
-                 and all(pc.scale is None for pc in pieces) and layer.Cout > 32 and B * H * W >= MS1X1_MIN_PIX)
-        # wide trunk layers: deep 256-wide split-f16 kernel (weights by LDS-DMA, one barrier per K step)
-        big = (split and BIG_ENABLED and layer.G == 1 and pieces[0].scale is None and pieces[0].Cp % 32 == 0 and residual is None
-               and layer.post is None and layer.Cout % 128 == 0 and layer.Cout >= BIG_MIN_COUT and layer.Cin >= BIG_MIN_CIN
-               and B * Ho * Wo >= 256 * 128)
-        # ... or, for the standard dilations, ONE launch with the 4-way sum in registers (msblock_dil_f16.hip)
-        msdil = (split and MSDIL_ENABLED and layer.G == 3 and layer.kh == 3 and layer.kw == 3 and layer.pad == (1, 1)
-                 and layer.dils == (4, 8, 12) and layer.CoutP == 32 and pieces[0].Cp == 32 and residual is not None
-                 and pieces[0].scale is None and layer.act == ACT_RELU and layer.post is None
-                 and H * W * pieces[0].stride < 2 ** 29 and H * W * dst.stride < 2 ** 29)
-        if msdil:
-            lattice = False
-        assert pieces[0].presplit is None or msdil if not isinstance(pieces[0], PlanarPiece) else True, "%s: only the one-launch dilated group reads split-pair storage" % name
-        if msdil and pieces[0].presplit is not None:
+    def _apply_choice(self, layer, choice, p0):
+        """The weight packs the chosen kernel reads (_KIND), the layer attributes they are packed under, and the packing itself."""
+        needs, _, sfrag, _ = _KIND[choice.kind]
+        for flag in needs + (("need_big1",) if choice.big1 else ()) + (("need_split",) if choice.tail_frames else ()):
+            setattr(layer, flag, True)
+        if choice.kind == "conv_bf16:3x3" and self.train:
+            layer.need_flat = True       # kinv / the generic pack index the weight-gradient paths
+        if choice.kind == "conv_f16x3:msdil" and p0.presplit is not None:
             layer.k_perm = SPLIT_PAIR_PERM
-        if self.dyn_scales:     # kernels that read egne_conv_desc.dyn_scale: role-split / resident-weights / halo / flat
-            s1x1 = ms1x1 = big = lattice = msdil = c4h = False
-        # narrow-input 3x3 layers on wide maps: producer / consumer waves (conv3x3_rs_f16.hip) instead of the all-in-one halo kernel
-        rs = (split and RS_ENABLED and HALO_F16_ENABLED and not lattice and not msdil and layer.kh == 3 and layer.kw == 3
-              and layer.G == 1 and layer.pad == (1, 1) and layer.stride == 1 and layer.pad_mode == 0 and layer.dils[0] == 1
-              and len(pieces) == 1 and W >= (RS_MIN_W_F16 if self.f16_products == 1 else RS_MIN_W) and H * W * max(pieces[0].stride, dst.stride) < 2 ** 29
-              and (residual is None or H * W * residual.stride < 2 ** 29))
-        # wider inputs: the resident-weights kernel with its weights streamed chunk by chunk (no statistics from its epilogue)
-        # (measured against the halo kernel: ahead for 128 -> 32 at 120x160 (290 vs 318 us), level or behind at 60x80 and for wide
-        #  outputs -- every output block stages the input again --, so only single-block layers on wide maps take it by default)
-        layer.halo_wide96 = False      # (the routing rules below see the 64-multiple row count; decided once the kernel is known)
-        rw_wide = (rs and RW_ENABLED and 64 < pieces[0].Cp <= RW_MAX_CP and layer.sfrag_coutp() <= RW_MAX_COUTP and not stats
-                   and W >= (RW_MIN_W_F16 if self.f16_products == 1 else RW_MIN_W) and min(layer.Cout_store, dst.Cp) % 8 == 0 and dst.stride % 4 == 0 and dst.off % 4 == 0
-                   and (residual is None or (residual.stride % 4 == 0 and residual.off % 4 == 0)))
-        rs = rw_wide or (rs and 8 <= pieces[0].Cp <= 64 and layer.sfrag_coutp() in (32, 64, 128)
-                         and not (pieces[0].Cp <= 32 and layer.sfrag_coutp() == 128))
-        # a slice whose last 32-channel chunk holds <= 16 channels (38 -> 64 of ESF-Net's second down block): the halo kernel skips the
-        # zero half of that chunk's k-steps (3 of 4 for 40 channels), the role-split kernels' 16x16x32 MFMAs cannot
-        if rs and not rw_wide and TAIL16_HALO and 32 < pieces[0].Cp <= 64 and 0 < pieces[0].Cp % 32 <= 16:
-            rs = False
-        shalo = shalo or rs
-        if lattice or msdil:
-            shalo = True
-        if split and not shalo and halo and pieces[0].scale is not None and layer.CoutP <= 32 and W >= HALO_F16_MIN_W:
-            split = False            # narrow fused-affine layers: the fp32 halo kernel beats the flat split kernel
-        if smallcin:
-            split = shalo = False
-        # small problems (one or two frames at the deep levels): 64-wide tiles + split-K on the flat kernel (conv_f16x3.hip small_plan)
-        small_ws = -1
-        if SMALL_ENABLED and split and not self.train and layer.G == 1 and not (lattice or msdil):
-            dq = _lib.ConvDesc()
-            dq.B, dq.Ho, dq.Wo, dq.kh, dq.kw, dq.ngroups, dq.CoutP = B, Ho, Wo, layer.kh, layer.kw, 1, layer.split_coutp()
-            dq.seg[0].Cp = pieces[0].Cp
-            small_ws = int(self.L.egne_conv2d_f16x3_small_workspace_floats(C.byref(dq)))
-        small = small_ws >= 0
-        if small and stats and STATS_FUSED and shalo and dst.Cp == min(layer.Cout_store, dst.Cp):
-            tall_ = ((H + 31) // 32) * ((W + 7) // 8) < ((W + 31) // 32) * ((H + 7) // 8)
-            if rs or (layer.dils[0] == 1 and not tall_):
-                small = False            # the halo / role-split kernel writes the consumer's InstanceNorm sums from its epilogue: one launch
-        if small:
-            shalo = rs = big = False
-        if smallcin or split:
-            halo = False
-        big_tail = 0     # frames handed to the 128x128 kernel so that the 256x256 launch fills whole rounds of 256 CUs
-        if big:
-            smallcin = shalo = halo = lattice = s1x1 = False
-            layer.need_big = True
-            layer.need_flat = True
-            big1 = BIG1_ENABLED and self.f16_products == 1 and (pad32(layer.Ktot) // 32 * layer.kh * layer.kw) % 2 == 0
-            if big1:
-                layer.need_big1 = True
-            bn = 256 if layer.Cout % 256 == 0 else 128
-            ny = (layer.Cout + bn - 1) // bn
-            wgs = lambda nb: (nb * Ho * Wo + 255) // 256 * ny      # noqa: E731
-            full = wgs(B) // BIG_CUS
-            if BIG_SPLIT_TAIL and full >= 1 and 0.04 < wgs(B) / BIG_CUS - full < 0.65:
-                b1 = B
-                while b1 > 1 and wgs(b1) > full * BIG_CUS:
-                    b1 -= 1
-                if wgs(b1) >= 0.9 * full * BIG_CUS:
-                    big_tail = B - b1
-                    layer.need_split = True
-        elif s1x1:
-            smallcin = split = shalo = halo = lattice = False
-            layer.need_s1 = True
-            layer.need_flat = True
-        elif ms1x1:
-            smallcin = split = shalo = halo = lattice = False
-            layer.need_m1 = True
-            layer.need_flat = True
-        elif smallcin and c4h:
-            layer.need_c4h = True
-            layer.need_flat = True
-        assert not isinstance(pieces[0], PlanarPiece) or (smallcin and c4h), "%s: only the first-layer streaming kernel reads planar inputs" % name
-        if False:
-            pass
-        elif smallcin:
-            layer.need_c4 = True
-            layer.need_flat = True   # the generic pack is still what the backward (wgrad) paths index with kinv
-        elif shalo:
-            # 96 outputs on the plain halo kernel (three products, dilation 1, no pooled second output): its 96-wide tile
-            layer.halo_wide96 = (layer.CoutP == 96 and not rs and not lattice and not msdil and layer.dils[0] == 1
-                                 and self.f16_products != 1 and getattr(self, "_pool_req", None) is None)
+        layer.halo_wide96 = choice.halo_wide96
+        if sfrag:
             layer.want_sfrag()
-        elif split and not big:
-            layer.need_split = True
-        elif halo:
-            layer.need_frag = True
-        else:
-            layer.need_flat = True
         if layer not in self.layers:
             self.layers.append(layer)
         layer.ensure_packed(self.device)
+
+    def _desc(self, layer, pieces, dst, B, H, W, Ho, Wo, residual=None, dtype=0):
+        """The generic egne_conv_desc of ``layer`` over ``pieces`` into ``dst`` (None: the first convolution of a fused pair, whose
+        result stays in LDS); Ktot, CoutP and the weight pack are the caller's."""
         d = _lib.ConvDesc()
+        d.dtype = dtype
         d.ovf_flag, d.f16_products = self.ovf_ptr(), self.f16_products
         d.B, d.H, d.W, d.Ho, d.Wo = B, H, W, Ho, Wo
         d.kh, d.kw, d.stride = layer.kh, layer.kw, layer.stride
@@ -1312,220 +1371,101 @@ class Plan:
         d.nseg = len(pieces)
         for i, p in enumerate(pieces):
             s = d.seg[i]
-            s.ptr, s.pix_stride, s.ch_off, s.Cp = p.ptr, p.stride, p.off, (p.C if isinstance(p, PlanarPiece) else p.Cp)
+            s.ptr, s.pix_stride, s.ch_off, s.Cp = p.ptr, p.stride, p.off, p.Cp
             s.scale = p.scale.data_ptr() if p.scale is not None else None
             s.shift = p.shift.data_ptr() if p.shift is not None else None
             s.act_in = p.act_in
-        d.Ktot, d.CoutP = (pad32(layer.Ktot), layer.split_coutp()) if split else (layer.Ktot, layer.CoutP)
-        if big:
-            d.CoutP = layer.big_coutp
-        if shalo:
-            d.CoutP = layer.sfrag_coutp()
-        d.w = (layer.wimg.data_ptr() if big else (layer.fhi.data_ptr() if shalo else layer.whi.data_ptr())) if split else (layer.wf.data_ptr() if halo else layer.wp.data_ptr())
         d.bias = layer.bp.data_ptr() if layer.biases is not None else None
         d.act = layer.act
         if layer.post is not None:
             d.post_scale, d.post_shift = layer.post[0].data_ptr(), layer.post[1].data_ptr()
         if residual is not None:
             d.residual, d.res_pix_stride, d.res_ch_off = residual.ptr, residual.stride, residual.off
-        d.out, d.out_pix_stride, d.out_ch_off = dst.ptr, dst.stride, dst.off
-        d.Cout_store = min(layer.Cout_store, dst.Cp)
-        assert tuple(dst.buf.shape[1:3]) == (Ho, Wo), (name, tuple(dst.buf.shape), Ho, Wo)
+        if dst is not None:
+            d.out, d.out_pix_stride, d.out_ch_off = dst.ptr, dst.stride, dst.off
+            d.Cout_store = min(layer.Cout_store, dst.Cp)
+            assert tuple(dst.buf.shape[1:3]) == (Ho, Wo), (tuple(dst.buf.shape), Ho, Wo)
         self.keep.append(d)
-        flops = 2.0 * B * Ho * Wo * layer.Cout * layer.Cin * layer.kh * layer.kw * layer.G
-        # split-f16 kernels multiply their input by a power of two before the f16 split; for RAW inputs (no normalisation
-        # fused on load) that factor comes from the measured max |x| of the slices (calibration pass of Plan.run)
-        raw = all(pc.scale is None for pc in pieces)
-        cal3 = (3, list(pieces), B * H * W) if raw else None
-        cal2 = (2, list(pieces), B * H * W) if raw else None
-        if self.dyn_scales:
-            layer.stale_scale_ok = True
-        if self.dyn_scales and raw and split and not (smallcin and c4h):
-            self._dyn_slot(d, pieces, B, B * H * W, name)
-            cal3 = cal2 = None
-        any16 = getattr(pieces[0], "f16s", None) is not None or dst.f16s is not None
-        if any16 and big and big1:
-            big_tail = 0                      # (the flat kernel behind a ragged last round reads and writes fp32)
-        if any16 and not ((shalo and rs and not (big or ms1x1 or s1x1 or msdil or lattice)) or (smallcin and c4h and not big) or (big and big1)):
-            raise NeedsFp32Storage(name)      # only the resident-weights 3x3, the first-layer kernel and the plain-f16 deep trunk kernel know f16 storage
-        in3, out3 = getattr(pieces[0], "split3", None), dst.split3
+        return d
+
+    def _storage_rules(self, cv):
+        """Slices held as f16 (Piece.f16s) or in channel-order split-pair storage (Piece.split3) may only meet the kernels that read and
+        write that storage, in a calibrated plan: anything else raises NeedsFp32Storage before the convolution's first launch is added."""
+        choice, kind, layer, dst, p0, d = cv.choice, cv.choice.kind, cv.layer, cv.dst, cv.pieces[0], cv.d
+        big, rsrw = kind == "conv_f16x3:big", kind in ("conv_f16x3:rw", "conv_f16x3:rs")
+        calibrated = CALIBRATE and not self.dyn_scales and cv.raw
+        fin, fout = getattr(p0, "f16s", None), dst.f16s
+        if fin is not None or fout is not None:
+            # only the resident-weights 3x3, the first-layer kernel and the plain-f16 deep trunk kernel know f16 storage
+            if not (rsrw or kind == "conv_f16x3:first" or (big and choice.big1)) or (big and not calibrated):
+                raise NeedsFp32Storage(cv.name)
+            if rsrw and (not (kind == "conv_f16x3:rw" and self.f16_products == 1 and calibrated and layer.post is None and cv.residual is None)
+                         or (fout is None and choice.fused_pool)):
+                raise NeedsFp32Storage(cv.name)
+        in3, out3 = getattr(p0, "split3", None), dst.split3
         if in3 is not None or out3 is not None:
             # channel-order split-pair storage: written by the deep trunk kernel and its frame tail, read by them and by the plain halo kernel (32 outputs)
-            halo3 = (shalo and not rs and not lattice and not msdil and not big and not ms1x1 and not s1x1 and out3 is None and layer.dils[0] == 1
-                     and layer.sfrag_coutp() == 32 and not stats and getattr(self, "_pool_req", None) is None)
-            if not ((big or halo3) and not (big and big1) and self.f16_products != 1 and CALIBRATE and not self.dyn_scales and raw and not self.train
-                    and pieces[0].Cp % 32 == 0 and pieces[0].off % 32 == 0 and (out3 is None or (int(d.Cout_store) % 32 == 0 and dst.off % 32 == 0))):
-                raise NeedsFp32Storage(name)
-            if in3 is not None:
-                d.seg[0].presplit = 3
-                # the storage scale IS the launch's a_scale (argument 2 of the deep trunk kernel, 3 of the flat and halo kernels)
-                cal2 = (lambda args, vmax, in3=in3: args[:2] + (in3.value,) + args[3:], [], 0)
-                cal3 = (lambda args, vmax, in3=in3: args[:3] + (in3.value,) + args[4:], [], 0)
-        if big and big_tail:
-            # two launches over disjoint frame ranges: [0, B - tail) on the 256-wide kernel, the rest on the 128x128 kernel
-            layer.ensure_packed(self.device)
-            d2 = _lib.ConvDesc()
-            C.memmove(C.byref(d2), C.byref(d), C.sizeof(_lib.ConvDesc))
-            b1 = B - big_tail
-            d.B, d2.B = b1, big_tail
-            p0 = pieces[0]
-            d2.seg[0].ptr = p0.ptr + 4 * b1 * H * W * p0.stride
-            d2.out = dst.ptr + 4 * b1 * Ho * Wo * dst.stride
-            d2.Ktot, d2.CoutP = pad32(layer.Ktot), layer.split_coutp()
-            self.keep.append(d2)
-            self._add(self.L.egne_conv2d_f16_big1_fwd if big1 else self.L.egne_conv2d_f16x3_big_fwd,
-                      (C.byref(d), (layer.wimg1 if big1 else layer.wimg).data_ptr(), F16X3_ASCALE, layer.w_scale_big), name,
-                      flops=flops * b1 / B, kind="conv_f16x3:big", cal=cal2, ws=[(3, layer, "w_scale_big")])
-            self._add(self.L.egne_conv2d_f16x3_fwd, (C.byref(d2), layer.whi.data_ptr(), layer.wlo.data_ptr(), F16X3_ASCALE, layer.w_scale),
-                      name + ".tail", flops=flops * big_tail / B, kind="conv_f16x3:flat", cal=cal3, ws=[(4, layer, "w_scale")])
-            if out3 is not None:
-                self._split3_out([(len(self.calls) - 2, d), (len(self.calls) - 1, d2)], dst, B * Ho * Wo)
-        elif big:
-            if any16:
-                if not (CALIBRATE and not self.dyn_scales and raw):
-                    raise NeedsFp32Storage(name)
-                if dst.f16s is not None:
-                    cal2 = self._f16_out(d, layer, dst, B * Ho * Wo, cal2, pieces[0].f16s)
-                if pieces[0].f16s is not None:
-                    cal2 = self._f16_in(d, pieces[0].f16s, cal2, 2)
-            self._add(self.L.egne_conv2d_f16_big1_fwd if big1 else self.L.egne_conv2d_f16x3_big_fwd,
-                      (C.byref(d), (layer.wimg1 if big1 else layer.wimg).data_ptr(), F16X3_ASCALE, layer.w_scale_big), name,
-                      flops=flops, kind="conv_f16x3:big", cal=cal2, ws=[(3, layer, "w_scale_big")])
-            if out3 is not None:
-                self._split3_out([(len(self.calls) - 1, d)], dst, B * Ho * Wo)
-        elif ms1x1:
-            d.Ktot, d.CoutP = layer.m1_ktot, layer.m1_coutp
-            self._add(self.L.egne_conv1x1_ms_f16x3_fwd, (C.byref(d), layer.m1hi.data_ptr(), layer.m1lo.data_ptr(), F16X3_ASCALE,
-                                                         layer.w_scale_m1), name, flops=flops, kind="conv_f16x3:gemm1x1", cal=cal3, ws=[(4, layer, "w_scale_m1")])
-        elif s1x1:
-            if getattr(self, "_up_add", None) is not None:
-                P, ph, pw = self._up_add
-                assert (2 * ph, 2 * pw) == (H, W) and layer.act == ACT_NONE and P.Cp >= int(d.Cout_store) and tuple(P.buf.shape[:3]) == (B, ph, pw), name
-                d.Ho, d.Wo = ph, pw
-                d.residual, d.res_pix_stride, d.res_ch_off = P.ptr, P.stride, P.off
-            self._add(self.L.egne_conv1x1_f16x3_fwd, (C.byref(d), layer.s1hi.data_ptr(), layer.s1lo.data_ptr(), F16X3_ASCALE,
-                                                      layer.w_scale1), name, flops=flops, kind="conv_f16x3:stream1x1", cal=cal3, ws=[(4, layer, "w_scale1")])
-        elif msdil and scores is not None:
-            # the block's output is consumed by the stage's score heads only: they are evaluated in the epilogue and the
-            # 32-channel map is never stored (scores = (weights [2][32], constants [2], s, s1, accumulate))
-            cw_, cc_, s0_, s1_, accum = scores
-            d.out = None
-            cal3 = self._presplit_in(d, pieces, residual, cal3)
-            self._add(self.L.egne_msblock_dil_scores_f16_fwd, (C.byref(d), layer.fhi.data_ptr(), layer.flo.data_ptr(), F16X3_ASCALE,
-                                                               layer.w_scale, cw_.data_ptr(), cc_.data_ptr(), s0_.data_ptr(),
-                                                               s1_.data_ptr(), int(accum)), name, flops=flops,
-                      kind="conv_f16x3:msdil", cal=cal3, ws=[(4, layer, "w_scale")])
-        elif msdil:
-            cal3 = self._presplit_in(d, pieces, residual, cal3)
-            self._add(self.L.egne_msblock_dil_f16_fwd, (C.byref(d), layer.fhi.data_ptr(), layer.flo.data_ptr(), F16X3_ASCALE,
-                                                        layer.w_scale), name, flops=flops, kind="conv_f16x3:msdil", cal=cal3, ws=[(4, layer, "w_scale")])
-        elif lattice:
-            perf = 9 * layer.sfrag_coutp() * pad32(layer.Ktot)
-            for g in range(3):
-                dg = _lib.ConvDesc()
-                C.memmove(C.byref(dg), C.byref(d), C.sizeof(_lib.ConvDesc))
-                dg.ngroups = 1
-                dg.dil[0] = layer.dils[g]
-                dg.bias = layer.bp.data_ptr() + 4 * g * layer.CoutP if layer.biases is not None else None
-                if g > 0:   # accumulate onto the running sum
-                    dg.residual, dg.res_pix_stride, dg.res_ch_off = dst.ptr, dst.stride, dst.off
-                self.keep.append(dg)
-                self._add(self.L.egne_conv3x3_halo_f16_fwd, (C.byref(dg), layer.fhi.data_ptr() + 2 * g * perf,
-                                                             layer.flo.data_ptr() + 2 * g * perf, F16X3_ASCALE, layer.w_scale),
-                          name + ".g%d" % g, flops=flops / 3, kind="conv_f16x3:lattice", cal=cal3, ws=[(4, layer, "w_scale")])
-        elif shalo and rs:
-            pq = getattr(self, "_pool_req", None)
-            if (pq is not None and POOL_FUSED and pieces[0].Cp > 32 and layer.sfrag_coutp() >= 64 and layer.post is None
-                    and layer.act in (ACT_NONE, ACT_RELU, ACT_LEAKY) and pq.Cp >= int(d.Cout_store)):
-                d.pool_out, d.pool_pix_stride, d.pool_ch_off = pq.ptr, pq.stride, pq.off
-                self.last_pooled = True
-            th = 8 if pieces[0].Cp <= 32 else 4
-            nchunk = ((W + 31) // 32) * ((H + th - 1) // th) * (2 if (th == 4 and layer.sfrag_coutp() >= 64) else 4)
-            fuse_stats = stats and STATS_FUSED and dst.Cp == int(d.Cout_store)
-            # resident-weights form (conv3x3_rw_f16.hip) unless the layer writes InstanceNorm sums from its epilogue
-            # (measured at 240x320x64 against the register-ring form: 64 -> 32 566 vs 777 us, 64 -> 64 1070 vs 1170, 32 -> 32 318 vs 356,
-            #  32 -> 64 622 vs 740; 64 -> 128 at 120x160 525 vs 560)
-            rw = rw_wide or (RW_ENABLED and not fuse_stats
-                  and int(d.Cout_store) % 8 == 0 and dst.stride % 4 == 0 and dst.off % 4 == 0
-                  and (residual is None or (residual.stride % 4 == 0 and residual.off % 4 == 0)))
-            if fuse_stats:
-                ws = self._stats_ws(d, B, nchunk)
-            ps = dst.presplit
-            if (ps is not None and rw and raw and CALIBRATE and not self.dyn_scales and layer.post is None and residual is None
-                    and not self.last_pooled and int(d.Cout_store) % 32 == 0 and dst.off % 32 == 0):
-                # split-pair output: hi / lo halves of out * s, s from a bound on |out| taken when the launch is calibrated
-                d.out_split, d.out_split_scale = 1, ps.value
-                self.last_presplit = True
+            halo3 = (kind == "conv_f16x3:halo" and out3 is None and layer.dils[0] == 1
+                     and layer.sfrag_coutp() == 32 and not cv.stats and cv.pool is None)
+            if not ((big or halo3) and not (big and choice.big1) and self.f16_products != 1 and calibrated and not self.train
+                    and p0.Cp % 32 == 0 and p0.off % 32 == 0 and (out3 is None or (int(d.Cout_store) % 32 == 0 and dst.off % 32 == 0))):
+                raise NeedsFp32Storage(cv.name)
 
-                def cal_ps(args, vmax, d=d, layer=layer, ps=ps):
-                    with torch.no_grad():
-                        bound = vmax * float(layer.weights[0].detach().abs().sum(dim=(1, 2, 3)).max())
-                        if layer.biases is not None and layer.biases[0] is not None:
-                            bound += float(layer.biases[0].detach().abs().max())
-                    ps.value = d.out_split_scale = _a_scale_for(bound)
-                    return args[:3] + (_a_scale_for(vmax),) + args[4:]
-                cal3 = (cal_ps, list(pieces), B * H * W)
-            fin, fout = pieces[0].f16s, dst.f16s
-            if fin is not None or fout is not None:
-                if not (rw and self.f16_products == 1 and CALIBRATE and not self.dyn_scales and layer.post is None and residual is None and raw):
-                    raise NeedsFp32Storage(name)
-                if fout is not None:
-                    if d.pool_out:
-                        assert pq.f16s is fout, "%s: the pooled second output shares the main output's storage scale" % name
-                    cal3 = self._f16_out(d, layer, dst, B * Ho * Wo, cal3, fin)
-                elif d.pool_out:
-                    raise NeedsFp32Storage(name)
-                if fin is not None:
-                    cal3 = self._f16_in(d, fin, cal3, 3)
-            self._add(self.L.egne_conv3x3_rw_f16_fwd if rw else self.L.egne_conv3x3_rs_f16_fwd,
-                      (C.byref(d), layer.fhi.data_ptr(), layer.flo.data_ptr(), F16X3_ASCALE, layer.w_scale), name, flops=flops,
-                      kind="conv_f16x3:rw" if rw else "conv_f16x3:rs", cal=cal3, ws=[(4, layer, "w_scale")])
-            if fuse_stats:
-                self.last_stats = self._stats_finish(ws, d, B, H * W, nchunk, name)
-                stats = False
-        elif shalo:
-            tx, ty = (W + 31) // 32, (H + 7) // 8
-            tall = ((H + 31) // 32) * ((W + 7) // 8) < tx * ty          # the kernel would walk the map transposed
-            fuse_stats = stats and STATS_FUSED and layer.dils[0] == 1 and dst.Cp == int(d.Cout_store)
-            if tall and HALO_TALL:                 # the launcher's choice: the tiles (= statistics chunks) of the transposed walk
-                tx, ty = (H + 31) // 32, (W + 7) // 8
-            pq = getattr(self, "_pool_req", None)
-            if (pq is not None and POOL_FUSED and HALO_POOL and not lattice and not stats and layer.dils[0] == 1 and layer.post is None
-                    and residual is None and layer.act in (ACT_NONE, ACT_RELU, ACT_LEAKY) and pq.Cp >= int(d.Cout_store) and layer.sfrag_coutp() % 64 == 0
-                    and ((H + 1) // 2) * ((W + 1) // 2) * pq.stride < 2 ** 29):
-                d.pool_out, d.pool_pix_stride, d.pool_ch_off = pq.ptr, pq.stride, pq.off      # pool2 of vgg16_c.py:72 from conv2_2's epilogue
-                self.last_pooled = True
-            if fuse_stats:
-                ws = self._stats_ws(d, B, tx * ty * 4)
-            self._add(self.L.egne_conv3x3_halo_f16_fwd, (C.byref(d), layer.fhi.data_ptr(), layer.flo.data_ptr(), F16X3_ASCALE,
-                                                         layer.w_scale), name, flops=flops, kind="conv_f16x3:halo", cal=cal3, ws=[(4, layer, "w_scale")])
-            if fuse_stats:
-                self.last_stats = self._stats_finish(ws, d, B, H * W, tx * ty * 4, name)
-                stats = False
-        elif split and small:
-            wsb = self.vec(max(small_ws, 4))
-            self._add(self.L.egne_conv2d_f16x3_small_fwd, (C.byref(d), layer.whi.data_ptr(), layer.wlo.data_ptr(), F16X3_ASCALE,
-                                                           layer.w_scale, wsb.data_ptr(), small_ws), name, flops=flops,
-                      kind="conv_f16x3:small", cal=cal3, ws=[(4, layer, "w_scale")])
-        elif split:
-            self._add(self.L.egne_conv2d_f16x3_fwd, (C.byref(d), layer.whi.data_ptr(), layer.wlo.data_ptr(), F16X3_ASCALE,
-                                                     layer.w_scale), name, flops=flops, kind="conv_f16x3:flat", cal=cal3, ws=[(4, layer, "w_scale")])
-        elif smallcin and c4h:
-            d.CoutP = layer.c4_coutp
-            if dst.f16s is not None:
-                cal3 = self._f16_out(d, layer, dst, B * Ho * Wo, cal3, None)
-            self._add(self.L.egne_conv3x3_smallcin_f16_fwd, (C.byref(d), layer.c4hi.data_ptr(), layer.c4lo.data_ptr(), F16X3_ASCALE,
-                                                             layer.w_scale_c4), name, flops=flops, kind="conv_f16x3:first", cal=cal3, ws=[(4, layer, "w_scale_c4")])
-        elif smallcin:
-            self._add(self.L.egne_conv3x3_smallcin_fwd, (C.byref(d), layer.w40.data_ptr()), name, flops=flops, kind="conv3x3_smallcin")
-        elif halo:
-            self._add(self.L.egne_conv3x3_halo_fwd, (C.byref(d),), name, flops=flops, kind="conv3x3_halo")
-        else:
-            if self.dyn_scales and residual is None and int(d.Cout_store) >= dst.Cp:
-                d.absmax_out = self._publish_absmax(dst, B)       # a split-f16 3x3 usually reads this next
-            self._add(self.L.egne_conv2d_fwd, (C.byref(d),), name, flops=flops, kind="conv_igemm")
-        assert scores is None or msdil, "score fusion needs the one-launch MSBlock kernel (check Plan.msdil_ok first)"
-        if stats:
+    def _calibration(self, cv):
+        """split-f16 kernels multiply their input by a power of two before the f16 split; for RAW inputs (no normalisation fused on
+        load) that factor comes from the measured max |x| of the slices (calibration pass of Plan.run).  Leaves the calibration entry
+        for a launch whose a_scale is argument 2 (deep trunk kernel) in ``cv.cal2``, for argument 3 (the others) in ``cv.cal3``."""
+        B, H, W = cv.B, cv.H, cv.W
+        cv.cal3 = (3, list(cv.pieces), B * H * W) if cv.raw else None
+        cv.cal2 = (2, list(cv.pieces), B * H * W) if cv.raw else None
+        if self.dyn_scales:
+            cv.layer.stale_scale_ok = True
+        if self.dyn_scales and cv.raw and _KIND[cv.choice.kind][1]:
+            self._dyn_slot(cv.d, cv.pieces, B, B * H * W, cv.name)
+            cv.cal3 = cv.cal2 = None
+        in3 = getattr(cv.pieces[0], "split3", None)
+        if in3 is not None:
+            cv.d.seg[0].presplit = 3
+            # the storage scale IS the launch's a_scale (argument 2 of the deep trunk kernel, 3 of the flat and halo kernels)
+            cv.cal2 = (lambda args, vmax, in3=in3: args[:2] + (in3.value,) + args[3:], [], 0)
+            cv.cal3 = (lambda args, vmax, in3=in3: args[:3] + (in3.value,) + args[4:], [], 0)
+
+    def _conv_impl(self, layer, pieces, dst, B, H, W, residual, name, stats, scores, pool, up_add, partials):
+        """pieces: input Pieces in concat order; dst: output Piece.  Returns (Ho, Wo); with ``stats`` also leaves the
+        per-sample InstanceNorm (scale, shift) of the OUTPUT in ``self.last_stats`` -- from partial sums written by the
+        kernel's epilogue where the kernel can do that, from a separate statistics pass otherwise."""
+        assert len(pieces) == len(layer.in_layout) and len(pieces) <= _lib.MAXSEG, name
+        for p, (c, cp) in zip(pieces, layer.in_layout):
+            assert p.Cp == cp and p.C == c, (name, p.C, p.Cp, c, cp)
+        q = self._conv_query(layer, pieces, dst, B, H, W, residual, stats, scores, pool, up_add)
+        if self.bf16:
+            return self._conv_bf16(q, layer, pieces, dst, B, H, W, residual, name, stats, scores, up_add, partials)
+        choice = choose_conv(q, self.L)
+        kind, p0 = choice.kind, pieces[0]
+        planar = isinstance(p0, PlanarPiece)
+        assert not planar or kind == "conv_f16x3:first", "%s: only the first-layer streaming kernel reads planar inputs" % name
+        assert planar or p0.presplit is None or kind == "conv_f16x3:msdil", "%s: only the one-launch dilated group reads split-pair storage" % name
+        assert scores is None or kind == "conv_f16x3:msdil", "score fusion needs the one-launch MSBlock kernel (check Plan.msdil_ok first)"
+        assert up_add is None or kind == "conv_f16x3:stream1x1", "%s: an up-sampled addend needs the streaming 1x1 kernel (check Plan.stream1x1_ok first)" % name
+        self._apply_choice(layer, choice, p0)
+        Ho, Wo = layer.out_hw(H, W)
+        d = self._desc(layer, pieces, dst, B, H, W, Ho, Wo, residual)
+        if planar:
+            d.seg[0].Cp = p0.C                   # planar slices: the channel count itself
+        _, split, sfrag, _ = _KIND[kind]
+        big = kind == "conv_f16x3:big"
+        d.Ktot = pad32(layer.Ktot) if split else layer.Ktot
+        d.CoutP = layer.big_coutp if big else layer.sfrag_coutp() if sfrag else layer.split_coutp() if split else layer.CoutP
+        d.w = (layer.wimg if big else layer.fhi if sfrag else layer.whi if split else layer.wf if kind == "conv3x3_halo" else layer.wp).data_ptr()
+        cv = types.SimpleNamespace(choice=choice, layer=layer, pieces=pieces, dst=dst, d=d, B=B, H=H, W=W, Ho=Ho, Wo=Wo, residual=residual, name=name,
+                                   stats=stats, scores=scores, pool=pool, up_add=up_add, raw=all(pc.scale is None for pc in pieces),
+                                   flops=2.0 * B * Ho * Wo * layer.Cout * layer.Cin * layer.kh * layer.kw * layer.G)
+        self._storage_rules(cv)
+        self._calibration(cv)
+        took_stats = getattr(self, _KIND[kind][3])(cv)
+        if CHECK_DISPATCH:
+            self._check_dispatch(q, choice, name)
+        if stats and not took_stats:
             self.last_stats = self.norm_stats(dst, B, Ho * Wo, name=name + ".stats")[:2]
         if self.train:
             # the backward kernels index the exact-fp32 weight layout: undo what a split-f16 forward put into the descriptor
@@ -1535,6 +1475,256 @@ class Plan:
             db.seg[0].ptr, db.out = pieces[0].ptr, dst.ptr
             self.keep.append(db)
             self.tape.append(lambda bw: self._bw_conv(bw, layer, list(pieces), dst, db, B, H, W, Ho, Wo, name))
+        return Ho, Wo
+
+    # ---- emitters: one per kernel family (_KIND); each adds the launches of ``cv`` and returns True if it took the statistics along
+    def _emit_narrow_f32(self, cv):
+        layer, d, p0 = cv.layer, cv.d, cv.pieces[0]
+        cp32 = (p0.Cp + 31) // 32 * 32
+        wn = self.vec(9 * cp32 * 4)          # [tap][channel][4 outputs]: re-packed when the weight changes
+
+        def repack(layer=layer, wn=wn):
+            w = layer.weights[0].detach().to(torch.float32).contiguous()
+            _lib.check(self.L.egne_pack_conv3x3_narrow_weight(w.data_ptr(), layer.Cout, layer.Cin, wn.data_ptr(), _lib.stream_ptr()), "pack_conv3x3_narrow")
+        self.pre.append(VersionGuard([layer.weights[0]], repack))
+        # the kernel computes four outputs (two packed multiply-adds per operand: no more instructions than three) and stores the
+        # slice's padding channels as zeros, like every other convolution of the library (the pack's rows, the bias and the post
+        # affine beyond Cout are zero)
+        d.Ktot, d.CoutP, d.w = cp32, 4, wn.data_ptr()
+        assert int(self.L.egne_conv3x3_narrow_supported(C.byref(d))) == 1 and p0.act_in == ACT_NONE, cv.name
+        self._add(self.L.egne_conv3x3_narrow_fwd, (C.byref(d),), cv.name, flops=2.0 * cv.B * cv.H * cv.W * layer.Cout * layer.Cin * 9, kind="conv3x3_narrow")
+
+    def _emit_big(self, cv):
+        layer, d, dst, p0, choice, B = cv.layer, cv.d, cv.dst, cv.pieces[0], cv.choice, cv.B
+        npix, tail, cal2 = B * cv.Ho * cv.Wo, choice.tail_frames, cv.cal2
+        if dst.f16s is not None:                  # (f16 tensors: never with a frame tail, choose_conv)
+            cal2 = self._f16_out(d, layer, dst, npix, cal2, p0.f16s)
+        if getattr(p0, "f16s", None) is not None:
+            cal2 = self._f16_in(d, p0.f16s, cal2, 2)
+        launches = [(len(self.calls), d)]
+        if tail:
+            # two launches over disjoint frame ranges: [0, B - tail) on the 256-wide kernel, the rest on the 128x128 kernel
+            d2 = _lib.ConvDesc()
+            C.memmove(C.byref(d2), C.byref(d), C.sizeof(_lib.ConvDesc))
+            d.B, d2.B = B - tail, tail
+            d2.seg[0].ptr = p0.ptr + 4 * (B - tail) * cv.H * cv.W * p0.stride
+            d2.out = dst.ptr + 4 * (B - tail) * cv.Ho * cv.Wo * dst.stride
+            d2.Ktot, d2.CoutP = pad32(layer.Ktot), layer.split_coutp()
+            self.keep.append(d2)
+            launches.append((len(self.calls) + 1, d2))
+        self._add(self.L.egne_conv2d_f16_big1_fwd if choice.big1 else self.L.egne_conv2d_f16x3_big_fwd,
+                  (C.byref(d), (layer.wimg1 if choice.big1 else layer.wimg).data_ptr(), F16X3_ASCALE, layer.w_scale_big), cv.name,
+                  flops=cv.flops * (B - tail) / B if tail else cv.flops, kind="conv_f16x3:big", cal=cal2, ws=[(3, layer, "w_scale_big")])
+        if tail:
+            self._add(self.L.egne_conv2d_f16x3_fwd, (C.byref(d2), layer.whi.data_ptr(), layer.wlo.data_ptr(), F16X3_ASCALE, layer.w_scale),
+                      cv.name + ".tail", flops=cv.flops * tail / B, kind="conv_f16x3:flat", cal=cv.cal3, ws=[(4, layer, "w_scale")])
+        if dst.split3 is not None:
+            self._split3_out(launches, dst, npix)
+
+    def _emit_gemm1x1(self, cv):
+        layer, d = cv.layer, cv.d
+        d.Ktot, d.CoutP = layer.m1_ktot, layer.m1_coutp
+        self._add(self.L.egne_conv1x1_ms_f16x3_fwd, (C.byref(d), layer.m1hi.data_ptr(), layer.m1lo.data_ptr(), F16X3_ASCALE,
+                                                     layer.w_scale_m1), cv.name, flops=cv.flops, kind="conv_f16x3:gemm1x1", cal=cv.cal3, ws=[(4, layer, "w_scale_m1")])
+
+    def _emit_stream1x1(self, cv):
+        layer, d = cv.layer, cv.d
+        if cv.up_add is not None:
+            P, ph, pw = cv.up_add
+            assert (2 * ph, 2 * pw) == (cv.H, cv.W) and layer.act == ACT_NONE and P.Cp >= int(d.Cout_store) and tuple(P.buf.shape[:3]) == (cv.B, ph, pw), cv.name
+            d.Ho, d.Wo = ph, pw
+            d.residual, d.res_pix_stride, d.res_ch_off = P.ptr, P.stride, P.off
+        self._add(self.L.egne_conv1x1_f16x3_fwd, (C.byref(d), layer.s1hi.data_ptr(), layer.s1lo.data_ptr(), F16X3_ASCALE,
+                                                  layer.w_scale1), cv.name, flops=cv.flops, kind="conv_f16x3:stream1x1", cal=cv.cal3, ws=[(4, layer, "w_scale1")])
+
+    def _emit_msdil(self, cv):
+        layer, d = cv.layer, cv.d
+        cal3 = self._presplit_in(d, cv.pieces, cv.residual, cv.cal3)
+        fn, heads = self.L.egne_msblock_dil_f16_fwd, ()
+        if cv.scores is not None:
+            # the block's output is consumed by the stage's score heads only: they are evaluated in the epilogue and the
+            # 32-channel map is never stored (scores = (weights [2][32], constants [2], s, s1, accumulate))
+            cw_, cc_, s0_, s1_, accum = cv.scores
+            fn, heads, d.out = self.L.egne_msblock_dil_scores_f16_fwd, (cw_.data_ptr(), cc_.data_ptr(), s0_.data_ptr(), s1_.data_ptr(), int(accum)), None
+        self._add(fn, (C.byref(d), layer.fhi.data_ptr(), layer.flo.data_ptr(), F16X3_ASCALE, layer.w_scale) + heads, cv.name, flops=cv.flops,
+                  kind="conv_f16x3:msdil", cal=cal3, ws=[(4, layer, "w_scale")])
+
+    def _emit_lattice(self, cv):
+        layer, d, dst = cv.layer, cv.d, cv.dst
+        perf = 9 * layer.sfrag_coutp() * pad32(layer.Ktot)
+        for g in range(3):
+            dg = _lib.ConvDesc()
+            C.memmove(C.byref(dg), C.byref(d), C.sizeof(_lib.ConvDesc))
+            dg.ngroups = 1
+            dg.dil[0] = layer.dils[g]
+            dg.bias = layer.bp.data_ptr() + 4 * g * layer.CoutP if layer.biases is not None else None
+            if g > 0:   # accumulate onto the running sum
+                dg.residual, dg.res_pix_stride, dg.res_ch_off = dst.ptr, dst.stride, dst.off
+            self.keep.append(dg)
+            self._add(self.L.egne_conv3x3_halo_f16_fwd, (C.byref(dg), layer.fhi.data_ptr() + 2 * g * perf,
+                                                         layer.flo.data_ptr() + 2 * g * perf, F16X3_ASCALE, layer.w_scale),
+                      cv.name + ".g%d" % g, flops=cv.flops / 3, kind="conv_f16x3:lattice", cal=cv.cal3, ws=[(4, layer, "w_scale")])
+
+    def _emit_rs_rw(self, cv):
+        layer, d, dst, pieces, choice, pq = cv.layer, cv.d, cv.dst, cv.pieces, cv.choice, cv.pool
+        B, H, W, name, cal3 = cv.B, cv.H, cv.W, cv.name, cv.cal3
+        rw = choice.kind == "conv_f16x3:rw"
+        if choice.fused_pool:
+            d.pool_out, d.pool_pix_stride, d.pool_ch_off = pq.ptr, pq.stride, pq.off
+            self.last_pooled = True
+        th = 8 if pieces[0].Cp <= 32 else 4
+        nchunk = ((W + 31) // 32) * ((H + th - 1) // th) * (2 if (th == 4 and layer.sfrag_coutp() >= 64) else 4)
+        if choice.fused_stats:
+            ws = self._stats_ws(d, B, nchunk)
+        ps = dst.presplit
+        if (ps is not None and rw and cv.raw and CALIBRATE and not self.dyn_scales and layer.post is None and cv.residual is None
+                and not self.last_pooled and int(d.Cout_store) % 32 == 0 and dst.off % 32 == 0):
+            # split-pair output: hi / lo halves of out * s, s from a bound on |out| taken when the launch is calibrated
+            d.out_split, d.out_split_scale = 1, ps.value
+            self.last_presplit = True
+
+            def cal_ps(args, vmax, d=d, layer=layer, ps=ps):
+                with torch.no_grad():
+                    bound = vmax * float(layer.weights[0].detach().abs().sum(dim=(1, 2, 3)).max())
+                    if layer.biases is not None and layer.biases[0] is not None:
+                        bound += float(layer.biases[0].detach().abs().max())
+                ps.value = d.out_split_scale = _a_scale_for(bound)
+                return args[:3] + (_a_scale_for(vmax),) + args[4:]
+            cal3 = (cal_ps, list(pieces), B * H * W)
+        fin, fout = pieces[0].f16s, dst.f16s
+        if fout is not None:
+            assert not choice.fused_pool or pq.f16s is fout, "%s: the pooled second output shares the main output's storage scale" % name
+            cal3 = self._f16_out(d, layer, dst, B * cv.Ho * cv.Wo, cal3, fin)
+        if fin is not None:
+            cal3 = self._f16_in(d, fin, cal3, 3)
+        self._add(self.L.egne_conv3x3_rw_f16_fwd if rw else self.L.egne_conv3x3_rs_f16_fwd,
+                  (C.byref(d), layer.fhi.data_ptr(), layer.flo.data_ptr(), F16X3_ASCALE, layer.w_scale), name, flops=cv.flops,
+                  kind=choice.kind, cal=cal3, ws=[(4, layer, "w_scale")])
+        if choice.fused_stats:
+            self.last_stats = self._stats_finish(ws, d, B, H * W, nchunk, name)
+        return choice.fused_stats
+
+    def _emit_halo(self, cv):
+        layer, d, choice, pq, H, W = cv.layer, cv.d, cv.choice, cv.pool, cv.H, cv.W
+        tx, ty = (W + 31) // 32, (H + 7) // 8
+        if ((H + 31) // 32) * ((W + 7) // 8) < tx * ty and HALO_TALL:   # the launcher walks the map transposed: the tiles (= statistics chunks) of that walk
+            tx, ty = (H + 31) // 32, (W + 7) // 8
+        if choice.fused_pool:
+            d.pool_out, d.pool_pix_stride, d.pool_ch_off = pq.ptr, pq.stride, pq.off
+            self.last_pooled = True
+        if choice.fused_stats:
+            ws = self._stats_ws(d, cv.B, tx * ty * 4)
+        self._add(self.L.egne_conv3x3_halo_f16_fwd, (C.byref(d), layer.fhi.data_ptr(), layer.flo.data_ptr(), F16X3_ASCALE,
+                                                     layer.w_scale), cv.name, flops=cv.flops, kind="conv_f16x3:halo", cal=cv.cal3, ws=[(4, layer, "w_scale")])
+        if choice.fused_stats:
+            self.last_stats = self._stats_finish(ws, d, cv.B, H * W, tx * ty * 4, cv.name)
+        return choice.fused_stats
+
+    def _emit_small(self, cv):
+        layer, small_ws = cv.layer, cv.choice.small_ws
+        wsb = self.vec(max(small_ws, 4))
+        self._add(self.L.egne_conv2d_f16x3_small_fwd, (C.byref(cv.d), layer.whi.data_ptr(), layer.wlo.data_ptr(), F16X3_ASCALE,
+                                                       layer.w_scale, wsb.data_ptr(), small_ws), cv.name, flops=cv.flops,
+                  kind="conv_f16x3:small", cal=cv.cal3, ws=[(4, layer, "w_scale")])
+
+    def _emit_flat(self, cv):
+        self._add(self.L.egne_conv2d_f16x3_fwd, (C.byref(cv.d), cv.layer.whi.data_ptr(), cv.layer.wlo.data_ptr(), F16X3_ASCALE,
+                                                 cv.layer.w_scale), cv.name, flops=cv.flops, kind="conv_f16x3:flat", cal=cv.cal3, ws=[(4, cv.layer, "w_scale")])
+
+    def _emit_first(self, cv):
+        layer, d, cal3 = cv.layer, cv.d, cv.cal3
+        d.CoutP = layer.c4_coutp
+        if cv.dst.f16s is not None:
+            cal3 = self._f16_out(d, layer, cv.dst, cv.B * cv.Ho * cv.Wo, cal3, None)
+        self._add(self.L.egne_conv3x3_smallcin_f16_fwd, (C.byref(d), layer.c4hi.data_ptr(), layer.c4lo.data_ptr(), F16X3_ASCALE,
+                                                         layer.w_scale_c4), cv.name, flops=cv.flops, kind="conv_f16x3:first", cal=cal3, ws=[(4, layer, "w_scale_c4")])
+
+    def _emit_smallcin(self, cv):
+        self._add(self.L.egne_conv3x3_smallcin_fwd, (C.byref(cv.d), cv.layer.w40.data_ptr()), cv.name, flops=cv.flops, kind="conv3x3_smallcin")
+
+    def _emit_halo_f32(self, cv):
+        self._add(self.L.egne_conv3x3_halo_fwd, (C.byref(cv.d),), cv.name, flops=cv.flops, kind="conv3x3_halo")
+
+    def _emit_igemm(self, cv):
+        if self.dyn_scales and cv.residual is None and int(cv.d.Cout_store) >= cv.dst.Cp:
+            cv.d.absmax_out = self._publish_absmax(cv.dst, cv.B)       # a split-f16 3x3 usually reads this next
+        self._add(self.L.egne_conv2d_fwd, (C.byref(cv.d),), cv.name, flops=cv.flops, kind="conv_igemm")
+
+    def _emit_bf16_3x3(self, cv):
+        self._add(self.L.egne_conv3x3_bf16_fwd, (C.byref(cv.d), cv.layer.bfrag.data_ptr()), cv.name, flops=cv.flops, kind="conv_bf16:3x3")
+        self._last_b3_desc = cv.d               # (a data gradient may get its slice's mask later: _bw_conv)
+
+    def _emit_bf16_1x1(self, cv):
+        self._add(self.L.egne_conv1x1_bf16_fwd, (C.byref(cv.d), cv.layer.b1frag.data_ptr()), cv.name, flops=cv.flops, kind="conv_bf16:1x1")
+
+    def _emit_bf16_narrow(self, cv):
+        self._add(self.L.egne_conv_narrow_bf16_fwd, (C.byref(cv.d),), cv.name, flops=cv.flops, kind="conv_bf16:narrow")
+
+    def _conv_bf16(self, q, layer, pieces, dst, B, H, W, residual, name, stats, scores, up_add, partials):
+        """Convolutions of a plan with bf16 activation storage: the 3x3 "same" convolutions over one slice run on bf16 MFMAs
+        (conv3x3_bf16.hip: weights rounded to bf16, fp32 accumulate), first layers (Cin <= 4) on the taps-in-K kernel and
+        everything else (1x1 over several slices, strided / reflect-padded / valid convolutions, linear layers) on the exact-fp32
+        implicit GEMM reading and writing bf16 (egne_conv_desc.dtype = 1).  No pre-scales, no calibration: bf16 has fp32's range."""
+        assert scores is None and layer.G == 1 and not isinstance(pieces[0], PlanarPiece), name
+        assert dst.buf.dtype == torch.bfloat16 and all(p.buf.dtype == torch.bfloat16 for p in pieces), name
+        choice = choose_conv(q, self.L)
+        self._apply_choice(layer, choice, pieces[0])
+        Ho, Wo = layer.out_hw(H, W)
+        d = self._desc(layer, pieces, dst, B, H, W, Ho, Wo, residual, dtype=1)
+        wp = getattr(layer, "wp", None)           # (a 3x3 needs no flat pack outside training; a bf16 data-gradient layer never has one)
+        d.Ktot, d.CoutP, d.w = layer.Ktot, layer.CoutP, (wp.data_ptr() if wp is not None else None)
+        if choice.kind == "conv_igemm" and BF16_NARROW:
+            # k x k onto <= 8 channels: the LDS-halo kernel, if it takes the descriptor of the implicit GEMM (the same flat pack)
+            q.narrow_bf16_ok = int(self.L.egne_conv_narrow_bf16_supported(C.byref(d)))
+            choice = choose_conv(q, self.L)
+        kind = choice.kind
+        if kind == "conv_bf16:3x3":
+            d.Ktot, d.w = pad32(layer.Ktot), None
+        assert up_add is None or (kind == "conv_bf16:1x1" and residual is None and layer.act == ACT_NONE), "%s: an up-sampled addend needs the streaming bf16 1x1 kernel" % name
+        db = None
+        if self.train:          # the backward descriptor: the plain convolution (an up-sampled addend has a backward of its own below)
+            db = _lib.ConvDesc()
+            C.memmove(C.byref(db), C.byref(d), C.sizeof(_lib.ConvDesc))
+            db.Ktot, db.CoutP = layer.Ktot, layer.CoutP
+            self.keep.append(db)
+        # statistics of the consumer's normalisation from this launch's epilogue (bf16 3x3: per-(tile, consumer wave) partial sums of what is
+        # stored, egne_conv_desc.stats_ws): `stats` (InstanceNorm: finished per sample below) or the caller's `partials` (BatchNorm:
+        # the caller finishes over its sample range, esf_engine._train_bn)
+        ws_stats, self.last_partials = None, None
+        if (stats or partials) and kind == "conv_bf16:3x3" and STATS_FUSED and STATS_FUSED_BF16 and self.train:
+            nchunk_s = ((W + 31) // 32) * ((H + 7) // 8) * 4
+            ws_stats = self._stats_ws(d, B, nchunk_s)
+            if partials:
+                self.last_partials = (ws_stats, nchunk_s, int(d.Cout_store))
+        if up_add is not None:
+            # dst = conv1x1(pieces) + b + up2x(P): P [B][H/2][W/2] in bf16, egne_conv1x1_bf16_fwd's half-resolution "residual"
+            P, ph, pw = up_add
+            assert (2 * ph, 2 * pw) == (H, W) and P.Cp >= int(d.Cout_store) and tuple(P.buf.shape[:3]) == (B, ph, pw) and P.off % 8 == 0 and P.stride % 8 == 0, name
+            d.Ho, d.Wo = ph, pw
+            d.residual, d.res_pix_stride, d.res_ch_off = P.ptr, P.stride, P.off
+        cv = types.SimpleNamespace(choice=choice, layer=layer, d=d, dst=dst, B=B, residual=residual, name=name,
+                                   flops=2.0 * B * Ho * Wo * layer.Cout * layer.Cin * layer.kh * layer.kw)
+        getattr(self, _KIND[kind][3])(cv)
+        if CHECK_DISPATCH:
+            self._check_dispatch(q, choice, name)
+        if stats:
+            self.last_stats = (self._stats_finish(ws_stats, d, B, Ho * Wo, nchunk_s, name) if ws_stats is not None
+                               else self.norm_stats(dst, B, Ho * Wo, name=name + ".stats")[:2])
+        if self.train:
+            def emit(bw, up_add=up_add):
+                self._bw_conv(bw, layer, list(pieces), dst, db, B, H, W, Ho, Wo, name)
+                if up_add is not None:
+                    # gP (+)= up2x^T(gz): gz = the gradient of dst as _bw_conv left it (the layer has no activation); the first of P's
+                    # readers to come by stores (no zero pass for P's twin)
+                    P, ph, pw = up_add
+                    Pq = Piece(P.buf, P.off, min(P.C, int(db.Cout_store)), int(db.Cout_store), P.n0)
+                    first = self.first_touch(Pq.buf, Pq.off, Pq.Cp, Pq.n0, B)
+                    gz, gP = self.gp(dst, B), self.gp(Pq, B)
+                    if first:
+                        self.mark_stored(Pq, B)
+                    bw.raw(self.L.egne_upsample2x_bwd_store if first else self.L.egne_upsample2x_bwd,
+                           (gz.ptr, gz.stride, gz.off, gP.ptr, gP.stride, gP.off, B, ph, pw, Pq.Cp), name + ".up_add.bwd")
+            self.tape.append(emit)
         return Ho, Wo
 
     def _f16_out(self, d, layer, dst, npix, cal, fin):
@@ -1590,146 +1780,6 @@ class Plan:
         d.seg[0].presplit = 1
         return (lambda args, vmax, ps=ps: args[:3] + (ps.value,) + args[4:], [], 0)
 
-    def _conv_bf16(self, layer, pieces, dst, B, H, W, residual, name, stats, scores):
-        """Convolutions of a plan with bf16 activation storage: the 3x3 "same" convolutions over one slice run on bf16 MFMAs
-        (conv3x3_bf16.hip: weights rounded to bf16, fp32 accumulate), first layers (Cin <= 4) on the taps-in-K kernel and
-        everything else (1x1 over several slices, strided / reflect-padded / valid convolutions, linear layers) on the exact-fp32
-        implicit GEMM reading and writing bf16 (egne_conv_desc.dtype = 1).  No pre-scales, no calibration: bf16 has fp32's range."""
-        assert scores is None and layer.G == 1 and not isinstance(pieces[0], PlanarPiece), name
-        Ho, Wo = layer.out_hw(H, W)
-        one = len(pieces) == 1 and layer.stride == 1 and layer.pad_mode == 0 and layer.dils[0] == 1 and layer.kh == 3 and layer.kw == 3 \
-            and layer.pad == (1, 1)
-        smallcin = (one and SMALLCIN_ENABLED and layer.Cin <= 4 and pad8(layer.Cout) <= 64 and pieces[0].scale is None and residual is None
-                    and not isinstance(layer, (DgradLayer, SplitDgradLayer, BfDgradLayer)) and layer.post is None)
-        fast3 = (one and not smallcin and BF16_FAST3X3 and layer.post is None and pieces[0].Cp % 8 == 0 and pieces[0].off % 8 == 0 and pieces[0].stride % 8 == 0
-                 and layer.CoutP <= 256 and min(layer.Cout_store, dst.Cp) % 4 == 0 and min(layer.Cout_store, dst.Cp) >= 8
-                 and H * W * max(pieces[0].stride, dst.stride) < 2 ** 30
-                 and (residual is None or H * W * residual.stride < 2 ** 30))
-        # 1x1 over raw slices: streaming bf16-MFMA kernel (conv1x1_bf16.hip); its weights must fit LDS (k-steps x blocks x 1 KB)
-        fast1 = (BF16_FAST1X1 and layer.kh == 1 and layer.kw == 1 and layer.stride == 1 and layer.pad == (0, 0) and layer.post is None
-                 and all(p.scale is None and p.Cp % 8 == 0 and p.off % 8 == 0 and p.stride % 8 == 0 for p in pieces)
-                 and B * H * W >= 4096 and min(layer.Cout_store, dst.Cp) % 8 == 0 and dst.off % 8 == 0 and dst.stride % 8 == 0
-                 and (residual is None or (residual.off % 8 == 0 and residual.stride % 8 == 0)))
-        if fast1:
-            dq = _lib.ConvDesc()
-            dq.nseg, dq.CoutP, dq.Ktot = len(pieces), layer.CoutP, layer.Ktot
-            for i, p in enumerate(pieces):
-                dq.seg[i].Cp = p.Cp
-            fast1 = int(self.L.egne_conv1x1_bf16_pack_elems(C.byref(dq))) > 0
-        if smallcin:
-            layer.need_c4 = True
-            layer.need_flat = True
-        elif fast3:
-            layer.need_bfrag = True
-            if self.train:
-                layer.need_flat = True       # kinv / the generic pack index the weight-gradient paths
-        elif fast1:
-            layer.need_flat = True
-            layer.need_b1 = True
-        else:
-            layer.need_flat = True
-        up_add = getattr(self, "_up_add", None)
-        assert up_add is None or (fast1 and residual is None and layer.act == ACT_NONE), "%s: an up-sampled addend needs the streaming bf16 1x1 kernel" % name
-        if layer not in self.layers:
-            self.layers.append(layer)
-        layer.ensure_packed(self.device)
-        d = _lib.ConvDesc()
-        d.dtype = 1
-        d.B, d.H, d.W, d.Ho, d.Wo = B, H, W, Ho, Wo
-        d.kh, d.kw, d.stride = layer.kh, layer.kw, layer.stride
-        d.pad_h, d.pad_w, d.pad_mode = layer.pad[0], layer.pad[1], layer.pad_mode
-        d.ngroups = 1
-        for g in range(_lib.MAXGROUP):
-            d.dil[g] = layer.dils[0] if g == 0 else 1
-        d.nseg = len(pieces)
-        for i, p in enumerate(pieces):
-            sg = d.seg[i]
-            sg.ptr, sg.pix_stride, sg.ch_off, sg.Cp = p.ptr, p.stride, p.off, p.Cp
-            sg.scale = p.scale.data_ptr() if p.scale is not None else None
-            sg.shift = p.shift.data_ptr() if p.shift is not None else None
-            sg.act_in = p.act_in
-        d.Ktot, d.CoutP = (pad32(layer.Ktot) if fast3 else layer.Ktot), layer.CoutP
-        d.w = None if fast3 else layer.wp.data_ptr()
-        d.bias = layer.bp.data_ptr() if layer.biases is not None else None
-        d.act = layer.act
-        if layer.post is not None:
-            d.post_scale, d.post_shift = layer.post[0].data_ptr(), layer.post[1].data_ptr()
-        if residual is not None:
-            d.residual, d.res_pix_stride, d.res_ch_off = residual.ptr, residual.stride, residual.off
-        d.out, d.out_pix_stride, d.out_ch_off = dst.ptr, dst.stride, dst.off
-        d.Cout_store = min(layer.Cout_store, dst.Cp)
-        assert tuple(dst.buf.shape[1:3]) == (Ho, Wo), (name, tuple(dst.buf.shape), Ho, Wo)
-        assert dst.buf.dtype == torch.bfloat16 and all(p.buf.dtype == torch.bfloat16 for p in pieces), name
-        self.keep.append(d)
-        flops = 2.0 * B * Ho * Wo * layer.Cout * layer.Cin * layer.kh * layer.kw
-        db = None
-        if self.train:          # the backward descriptor: the plain convolution (an up-sampled addend has a backward of its own below)
-            db = _lib.ConvDesc()
-            C.memmove(C.byref(db), C.byref(d), C.sizeof(_lib.ConvDesc))
-            db.Ktot, db.CoutP = layer.Ktot, layer.CoutP
-            self.keep.append(db)
-        # statistics of the consumer's normalisation from this launch's epilogue (bf16 3x3: per-(tile, consumer wave) partial sums of what is
-        # stored, egne_conv_desc.stats_ws): `stats` (InstanceNorm: finished per sample below) or the caller's `_want_partials` (BatchNorm:
-        # the caller finishes over its sample range, esf_engine._train_bn)
-        ws_stats, want_partials = None, bool(getattr(self, "_want_partials", False))
-        self._want_partials, self.last_partials = False, None
-        if (stats or want_partials) and fast3 and STATS_FUSED and STATS_FUSED_BF16 and self.train:
-            nchunk_s = ((W + 31) // 32) * ((H + 7) // 8) * 4
-            ws_stats = self._stats_ws(d, B, nchunk_s)
-            if want_partials:
-                self.last_partials = (ws_stats, nchunk_s, int(d.Cout_store))
-        if up_add is not None:
-            # dst = conv1x1(pieces) + b + up2x(P): P [B][H/2][W/2] in bf16, egne_conv1x1_bf16_fwd's half-resolution "residual"
-            P, ph, pw = up_add
-            assert (2 * ph, 2 * pw) == (H, W) and P.Cp >= int(d.Cout_store) and tuple(P.buf.shape[:3]) == (B, ph, pw) and P.off % 8 == 0 and P.stride % 8 == 0, name
-            d.Ho, d.Wo = ph, pw
-            d.residual, d.res_pix_stride, d.res_ch_off = P.ptr, P.stride, P.off
-        if smallcin:
-            self._add(self.L.egne_conv3x3_smallcin_fwd, (C.byref(d), layer.w40.data_ptr()), name, flops=flops, kind="conv3x3_smallcin")
-        elif fast3:
-            self._add(self.L.egne_conv3x3_bf16_fwd, (C.byref(d), layer.bfrag.data_ptr()), name, flops=flops, kind="conv_bf16:3x3")
-            self._last_b3_desc = d               # (a data gradient may get its slice's mask later: _bw_conv)
-        elif fast1:
-            self._add(self.L.egne_conv1x1_bf16_fwd, (C.byref(d), layer.b1frag.data_ptr()), name, flops=flops, kind="conv_bf16:1x1")
-        elif BF16_NARROW and int(self.L.egne_conv_narrow_bf16_supported(C.byref(d))):
-            # k x k onto <= 8 channels (the data gradient of the StyleEncoder's 7x7): LDS-halo kernel instead of 98 implicit-GEMM steps
-            self._add(self.L.egne_conv_narrow_bf16_fwd, (C.byref(d),), name, flops=flops, kind="conv_bf16:narrow")
-        else:
-            self._add(self.L.egne_conv2d_fwd, (C.byref(d),), name, flops=flops, kind="conv_igemm")
-        if stats:
-            self.last_stats = (self._stats_finish(ws_stats, d, B, Ho * Wo, nchunk_s, name) if ws_stats is not None
-                               else self.norm_stats(dst, B, Ho * Wo, name=name + ".stats")[:2])
-        if self.train:
-            def emit(bw, up_add=up_add):
-                self._bw_conv(bw, layer, list(pieces), dst, db, B, H, W, Ho, Wo, name)
-                if up_add is not None:
-                    # gP (+)= up2x^T(gz): gz = the gradient of dst as _bw_conv left it (the layer has no activation); the first of P's
-                    # readers to come by stores (no zero pass for P's twin)
-                    P, ph, pw = up_add
-                    Pq = Piece(P.buf, P.off, min(P.C, int(db.Cout_store)), int(db.Cout_store), P.n0)
-                    first = self.first_touch(Pq.buf, Pq.off, Pq.Cp, Pq.n0, B)
-                    gz, gP = self.gp(dst, B), self.gp(Pq, B)
-                    if first:
-                        self.mark_stored(Pq, B)
-                    bw.raw(self.L.egne_upsample2x_bwd_store if first else self.L.egne_upsample2x_bwd,
-                           (gz.ptr, gz.stride, gz.off, gP.ptr, gP.stride, gP.off, B, ph, pw, Pq.Cp), name + ".up_add.bwd")
-            self.tape.append(emit)
-        return Ho, Wo
-
-    def bf16_stream1x1_ok(self, layer, pieces, dst, B, H, W):
-        """True if _conv_bf16 runs this 1x1 on the streaming bf16-MFMA kernel (conv1x1_bf16.hip) -- the one that can add an
-        up-sampled half-resolution tensor in its epilogue (``up_add``)."""
-        if not (self.bf16 and BF16_FAST1X1 and layer.kh == 1 and layer.kw == 1 and layer.stride == 1 and layer.pad == (0, 0) and layer.post is None
-                and all(p.scale is None and p.Cp % 8 == 0 and p.off % 8 == 0 and p.stride % 8 == 0 for p in pieces)
-                and B * H * W >= 4096 and min(layer.Cout_store, dst.Cp) % 8 == 0 and dst.off % 8 == 0 and dst.stride % 8 == 0
-                and len(pieces) <= _lib.MAXSEG):
-            return False
-        dq = _lib.ConvDesc()
-        dq.nseg, dq.CoutP, dq.Ktot = len(pieces), layer.CoutP, layer.Ktot
-        for i, p in enumerate(pieces):
-            dq.seg[i].Cp = p.Cp
-        return int(self.L.egne_conv1x1_bf16_pack_elems(C.byref(dq))) > 0
-
     def pair_fusable(self, l1, pieces, l2, dst, H, W):
         """True if conv_pair will run l2(l1(cat(pieces))) as ONE launch (conv_fused_1x1_3x3_f16.hip)."""
         return (FUSE_1X1 and F16X3_ENABLED and not self.train and not self.bf16 and l1.split1 and l2.split and l1.kh == 1 and l1.kw == 1
@@ -1758,22 +1808,10 @@ class Plan:
         if layer not in self.layers:
             self.layers.append(layer)
         layer.ensure_packed(self.device)
-        d = _lib.ConvDesc()
-        d.ovf_flag, d.f16_products = self.ovf_ptr(), self.f16_products
-        d.B, d.H, d.W, d.Ho, d.Wo = B, H, W, Ho, Wo
-        d.kh = d.kw = d.stride = d.ngroups = 1
-        d.nseg = len(pieces)
-        for i, p in enumerate(pieces):
-            sg = d.seg[i]
-            sg.ptr, sg.pix_stride, sg.ch_off, sg.Cp = p.ptr, p.stride, p.off, p.Cp
-            sg.scale, sg.shift, sg.act_in = p.scale.data_ptr(), p.shift.data_ptr(), p.act_in
+        assert tuple(layer.pad) == (0, 0) and layer.pad_mode == 0, name
+        d = self._desc(layer, pieces, dst, B, H, W, Ho, Wo)
+        d.dil[0:_lib.MAXGROUP] = (0,) * _lib.MAXGROUP      # (a 1x1: the kernel reads no dilation, the descriptor never carried one)
         d.Ktot, d.CoutP = layer.Ktot, layer.CoutP
-        d.bias = layer.bp.data_ptr() if layer.biases is not None else None
-        d.act = layer.act
-        d.out, d.out_pix_stride, d.out_ch_off = dst.ptr, dst.stride, dst.off
-        d.Cout_store = min(layer.Cout_store, dst.Cp)
-        assert tuple(dst.buf.shape[1:3]) == (Ho, Wo), (name, tuple(dst.buf.shape), Ho, Wo)
-        self.keep.append(d)
         flops = 2.0 * B * Ho * Wo * layer.Cout * layer.Cin
         # statistics chunks: runs of 32-pixel blocks of one frame, one wave each (conv1x1_pool_f16x3_kernel) -- as long as the launch
         # keeps TDPOOL_STATS_UNITS waves busy, at most 8 blocks; + a 32-pixel patch per wave behind the weights in LDS
@@ -1840,36 +1878,16 @@ class Plan:
             if l not in self.layers:
                 self.layers.append(l)
             l.ensure_packed(self.device)
-        d1, d2 = _lib.ConvDesc(), _lib.ConvDesc()
-        d2.ovf_flag, d2.f16_products = self.ovf_ptr(), self.f16_products
-        for d, l in ((d1, l1), (d2, l2)):
-            d.B, d.H, d.W, d.Ho, d.Wo = B, H, W, H, W
-            d.kh, d.kw, d.stride = l.kh, l.kw, 1
-            d.pad_h, d.pad_w, d.pad_mode, d.ngroups = l.pad[0], l.pad[1], 0, 1
-            for g in range(_lib.MAXGROUP):
-                d.dil[g] = 1
-            d.bias = l.bp.data_ptr() if l.biases is not None else None
-            d.act = l.act
-        d1.nseg = len(pieces)
-        for i, p in enumerate(pieces):
-            sg = d1.seg[i]
-            sg.ptr, sg.pix_stride, sg.ch_off, sg.Cp, sg.act_in = p.ptr, p.stride, p.off, p.Cp, ACT_NONE
+        d1 = self._desc(l1, pieces, None, B, H, W, H, W)
+        d1.ovf_flag, d1.f16_products = None, 0       # (the second descriptor carries them for the launch)
         d1.Ktot, d1.CoutP = l1.Ktot, l1.CoutP
         if up_add is not None:
             P, ph, pw = up_add
             assert (2 * ph, 2 * pw) == (H, W) and P.Cp >= 32 and tuple(P.buf.shape[:3]) == (B, ph, pw)
             d1.Ho, d1.Wo = ph, pw
             d1.residual, d1.res_pix_stride, d1.res_ch_off = P.ptr, P.stride, P.off
-        d2.nseg = 0
+        d2 = self._desc(l2, [], dst, B, H, W, H, W, residual)       # nseg = 0: the intermediate stays in LDS
         d2.Ktot, d2.CoutP = l1.CoutP, l2.sfrag_coutp()
-        if l2.post is not None:
-            d2.post_scale, d2.post_shift = l2.post[0].data_ptr(), l2.post[1].data_ptr()
-        if residual is not None:
-            d2.residual, d2.res_pix_stride, d2.res_ch_off = residual.ptr, residual.stride, residual.off
-        d2.out, d2.out_pix_stride, d2.out_ch_off = dst.ptr, dst.stride, dst.off
-        d2.Cout_store = min(l2.Cout_store, dst.Cp)
-        assert tuple(dst.buf.shape[1:3]) == (H, W), (name, tuple(dst.buf.shape), H, W)
-        self.keep += [d1, d2]
 
         def rescale(args, vmax, l1=l1, up_add=up_add):
             # a1 from the measured max of the slices; a2 from a bound on the 1x1 result: max|in| * max_co sum_c |w| + max|b|
@@ -1907,29 +1925,11 @@ class Plan:
                 self.layers.append(l)
             l.ensure_packed(self.device)
         assert l1.c4_coutp == 32
-        d1, d2 = _lib.ConvDesc(), _lib.ConvDesc()
-        d2.ovf_flag, d2.f16_products = self.ovf_ptr(), self.f16_products
-        for d, l in ((d1, l1), (d2, l2)):
-            d.B, d.H, d.W, d.Ho, d.Wo = B, H, W, H, W
-            d.kh, d.kw, d.stride = 3, 3, 1
-            d.pad_h, d.pad_w, d.pad_mode, d.ngroups = 1, 1, 0, 1
-            for g in range(_lib.MAXGROUP):
-                d.dil[g] = 1
-            d.bias = l.bp.data_ptr() if l.biases is not None else None
-            d.act = l.act
-        d1.nseg = 1
-        sg = d1.seg[0]
-        sg.ptr, sg.pix_stride, sg.ch_off, sg.Cp, sg.act_in = src.ptr, src.stride, src.off, src.Cp, ACT_NONE
+        d1 = self._desc(l1, [src], None, B, H, W, H, W)
+        d1.ovf_flag, d1.f16_products = None, 0       # (the second descriptor carries them for the launch)
         d1.Ktot, d1.CoutP = src.Cp, 32
-        d2.nseg = 0
+        d2 = self._desc(l2, [], dst, B, H, W, H, W, residual)       # nseg = 0: the intermediate stays in LDS
         d2.Ktot, d2.CoutP = 32, 32
-        if l2.post is not None:
-            d2.post_scale, d2.post_shift = l2.post[0].data_ptr(), l2.post[1].data_ptr()
-        if residual is not None:
-            d2.residual, d2.res_pix_stride, d2.res_ch_off = residual.ptr, residual.stride, residual.off
-        d2.out, d2.out_pix_stride, d2.out_ch_off = dst.ptr, dst.stride, dst.off
-        d2.Cout_store = min(l2.Cout_store, dst.Cp)
-        self.keep += [d1, d2]
         if C1V and isinstance(src, PlanarPiece) and l1.Cin == 1 and l1.Cout <= 32:
             # one-channel input: the first convolution on the vector ALU in exact fp32 (conv_fused_1x1_3x3_f16.hip, C1V); its weights as
             # a compact table [32][12] = nine taps, bias, two zeros per channel (scalar operands of the kernel)

@@ -115,7 +115,7 @@ def _train_bn(pl, bn, pre, dst, n0, B, HW, name, producer=None, hw=None, partial
     (egne_bn_act_bwd: no pass of its own for either)."""
     p, q = pre.samples(n0), dst.samples(n0)
     if partials is not None and partials[2] == pre.Cp:
-        # batch statistics from the partial sums the producing convolution left (engine.Plan._conv_bf16, `_want_partials`): the chunks of
+        # batch statistics from the partial sums the producing convolution left (engine.Plan.conv, `partials=True`): the chunks of
         # samples [n0, n0 + B) as ONE sample of B * nchunk chunks -- no pass over `pre`
         ws_, nch, Cs_ = partials
         rstd, nshift, mean, var = pl.vec(1, pre.Cp), pl.vec(1, pre.Cp), pl.vec(1, pre.Cp), pl.vec(1, pre.Cp)
@@ -283,9 +283,8 @@ def build_forward_plan(model, B, H, W, dev, training, dtype=torch.float32):
     else:
         pl.conv(l1, [xin_p], Piece(t0, 0, chz), NB, H, W, name="enc.head.conv1")
         pre = pl.buf(NB, H, W, pad8(chz))
-        pl._want_partials = True
-        pl.conv(l, [Piece(t0, 0, chz)], Piece(pre, 0, chz), NB, H, W, name="enc.head.conv2")
-        head_partials, pl._want_partials = pl.last_partials, False
+        pl.conv(l, [Piece(t0, 0, chz)], Piece(pre, 0, chz), NB, H, W, name="enc.head.conv2", partials=True)
+        head_partials = pl.last_partials
         pl.dbg["head_pre"] = pre
         _train_bn(pl, enc.head.bn, Piece(pre, 0, chz), D[0]["x"], 0, B, H * W, "enc.head.bn", producer=l, hw=(H, W), partials=head_partials)
         if add_edge:

@@ -464,8 +464,7 @@ def test_statistics_from_the_bf16_3x3_epilogue(G, B, Cin, Cout, H, W, bias, monk
     wp.grad, bp.grad = torch.zeros_like(wp), torch.zeros_like(bp)
     layer = ConvLayer([wp], [bp], [(xp.C, xp.Cp)], pad=(1, 1), act=2)
     out = pl.buf(B, H, W, pad8(Cout))
-    pl._want_partials = True
-    pl.conv(layer, [xp], Piece(out, 0, Cout), B, H, W, name="c", stats=True)
+    pl.conv(layer, [xp], Piece(out, 0, Cout), B, H, W, name="c", stats=True, partials=True)
     sc, sh = pl.last_stats
     ws, nchunk, Cs = pl.last_partials
     kinds = [m[0] for m in pl.meta]
