@@ -45,7 +45,9 @@ _DATA = (
                          "per-stage timers"),
     ("device_prep", int, 0, "1: distance maps computed from the labels on the GPU (egne_amd.dataprep) instead of taken "
                             "from the Dataset (CurriculumLib.py:131-136); 2: the boundary weights of CurriculumLib.py:128-129 too "
-                            "(parity unpinned: restated from OpenCV's published Canny / dilate)"),
+                            "(parity unpinned: restated from OpenCV's published Canny / dilate); 3: pupil_center, elNorm and cond "
+                            "too, from the reference's ElliFit + RANSAC on the label's boundaries (egne_amd.dataprep.ellipse_targets): "
+                            "(image, label) pairs are then enough"),
 )
 _OUTPUT = (
     ("expname", str, "dev", "sub-directory of logs/<model>/"),

@@ -11,6 +11,7 @@ videos/example1.avi) are decoded with PIL, results go to <video>_ellipses.npy in
     python evaluate.py --path2data videos --device_io 1 --device_jpeg 1     (frame number and Motion-JPEG encoding on the device too)
     python evaluate.py --path2data videos --device_io 1 --device_jpeg 1 --device_decode 1     (and the input's Motion-JPEG decoding)
     python evaluate.py --path2data videos --ellipse_seed mask     (ellipse seeds from the class map instead of the regression head)
+    python evaluate.py --path2data videos --ellipse_seed ransac   (seeds from the reference's ElliFit + RANSAC on the class map's boundaries)
 """
 import argparse
 import glob
@@ -45,7 +46,7 @@ def parse_args(argv=None):
     p.add_argument('--device_io', type=int, default=0, choices=(0, 1))   # 1: frame prep and overlay rendering on the device (csrc/evalio.hip)
     p.add_argument('--device_jpeg', type=int, default=0, choices=(0, 1))  # 1: frame number and JPEG encoding on the device too (csrc/jpeg.hip); needs --device_io 1
     p.add_argument('--device_decode', type=int, default=0, choices=(0, 1))  # 1: the input's JPEG decoding on the device (csrc/jpeg_decode.hip); needs --device_io 1
-    p.add_argument('--ellipse_seed', type=str, default='pred', choices=('pred', 'mask'))   # mask: the searches are seeded from the class map (csrc/mask_seed.hip)
+    p.add_argument('--ellipse_seed', type=str, default='pred', choices=('pred', 'mask', 'ransac'))   # mask: the searches are seeded from the class map (csrc/mask_seed.hip); ransac: from ElliFit + RANSAC on its boundaries (csrc/ellifit.hip)
     a = p.parse_args(argv)
     if a.device_jpeg and not a.device_io:
         p.error('--device_jpeg 1 encodes the frames that --device_io 1 renders on the device: it needs --device_io 1')
@@ -126,14 +127,24 @@ SEED_REGIONS = {'ritnet_v2': None,                          # utils.DEFAULT_SEED
                 'deepvog': ((0, 1), (0b010, 1))}            # class map {0, 1 = pupil}: no iris row, the pupil seeded from and scored against class 1
 
 
+RANSAC_REGIONS = {'ritnet_v2': None,                        # utils.DEFAULT_RANSAC_REGIONS: iris boundary of classes 1 | 2, pupil boundary away from class 0
+                  'deepvog': ((0, 1), (0b010, 1, 0))}
+
+
 def seed_of(args):
-    """(seed, regions) of --ellipse_seed / --model: ('pred', None) unless the flag asks for the class map."""
-    if args is None or getattr(args, 'ellipse_seed', 'pred') != 'mask':
-        return 'pred', None
-    return 'mask', SEED_REGIONS.get(getattr(args, 'model', 'ritnet_v2'))
+    """(seed, regions) of --ellipse_seed / --model: ('pred', None) unless the flag asks for the class map (mask: second moments of the
+    largest component; ransac: ElliFit + RANSAC on the region's boundary, generated draws with seed 0 -- the same for every call)."""
+    kind = 'pred' if args is None else getattr(args, 'ellipse_seed', 'pred')
+    if kind == 'mask':
+        return 'mask', SEED_REGIONS.get(getattr(args, 'model', 'ritnet_v2'))
+    if kind == 'ransac':
+        return 'ransac', RANSAC_REGIONS.get(getattr(args, 'model', 'ritnet_v2'))
+    return 'pred', None
 
 
 def _fit(mask, elPred, seed, regions):
+    if seed == 'ransac':
+        return fit_ellipses_from_mask(mask, regions, seed_kind='ransac')
     if seed == 'mask':
         return fit_ellipses_from_mask(mask, regions)
     return fit_ellipses_from_pred(mask, elPred)

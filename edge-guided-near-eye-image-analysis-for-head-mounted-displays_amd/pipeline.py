@@ -82,7 +82,8 @@ class WindowedFit:
     MI355X, B = 64, edge + seg + fit pipelined (scratch/ab_fit.sh): 1998-2001 frames/s released at once, 2009-2021 in a window.
 
     ``submit(mask, elPred, then=None, seed="pred", regions=None)`` is called on the stream that produced the two tensors (``seed="mask"``:
-    the seeds come from the class map, utils.fit_ellipses_from_mask with ``regions``, and elPred is not read); it returns a handle: ``result`` (device
+    the seeds come from the class map, utils.fit_ellipses_from_mask with ``regions``, and elPred is not read; ``seed="ransac"``: the same
+    with the seeds of utils.ellipse_ransac_from_mask, further keyword arguments go to it); it returns a handle: ``result`` (device
     tensor [F,2,5], valid once the handle is done), ``synchronize()`` (host waits; queues the searches at once if their window has not
     opened yet -- the last batches of a run), ``wait(stream)``.  ``then(result)`` runs on the search stream right behind the searches
     (e.g. the copy to pinned host memory)."""
@@ -129,11 +130,11 @@ class WindowedFit:
         except Exception:
             pass
 
-    def submit(self, mask, elPred, then=None, seed="pred", regions=None):
+    def submit(self, mask, elPred, then=None, seed="pred", regions=None, **ransac_args):
         from . import engine
         from .utils import fit_ellipses_from_mask, fit_ellipses_from_pred
-        if seed not in ("pred", "mask"):
-            raise ValueError("WindowedFit.submit: seed %r (pred or mask)" % (seed,))
+        if seed not in ("pred", "mask", "ransac"):
+            raise ValueError("WindowedFit.submit: seed %r (pred, mask or ransac)" % (seed,))
         ready = torch.cuda.Event()
         ready.record()
         h = WindowedFit.Handle()
@@ -145,7 +146,9 @@ class WindowedFit:
                 side.wait_event(window)
             with torch.cuda.stream(side), torch.no_grad():
                 mask.record_stream(side)
-                if seed == "mask":
+                if seed == "ransac":
+                    h.result = fit_ellipses_from_mask(mask, regions, seed_kind="ransac", **ransac_args)
+                elif seed == "mask":
                     h.result = fit_ellipses_from_mask(mask, regions)
                 else:
                     elPred.record_stream(side)

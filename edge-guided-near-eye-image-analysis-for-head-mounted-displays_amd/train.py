@@ -183,13 +183,16 @@ def main(argv=None):
                     if pipe is not None:
                         pipe.sa.wait_stream(torch.cuda.current_stream())
                 optimizer.zero_grad()
+                pc_u, eln_u, cond_u = pc.to(device), eln.to(device), cond.to(device).float()
                 if args.device_prep:    # bit-identical to the Dataset's one_hot2dist maps, 54k frames/s instead of 123 per host core
                     from egne_amd import dataprep
                     dm = dataprep.dist_maps(labels.to(device).long())
                     if args.device_prep >= 2:   # the boundary weights too (CurriculumLib.py:128-129; parity unpinned: no OpenCV to check against)
                         sw = dataprep.spatial_weights(labels.to(device).long())
-                out = model(img.to(device), edge, labels.to(device).long(), pc.to(device), eln.to(device), sw.to(device),
-                            dm.to(device), cond.to(device).float(), imInfo[:, 2].to(device), alpha)
+                    if args.device_prep >= 3:   # the ellipse targets too: the reference's ElliFit + RANSAC on the label's boundaries (csrc/ellifit.hip)
+                        pc_u, _, eln_u, cond_u = dataprep.ellipse_targets(labels.to(device).long())
+                out = model(img.to(device), edge, labels.to(device).long(), pc_u, eln_u, sw.to(device),
+                            dm.to(device), cond_u, imInfo[:, 2].to(device), alpha)
                 loss = out[3].mean()                                                   # train.py:285
                 loss.backward()
                 parallel.allreduce_grads(model)

@@ -341,11 +341,108 @@ def _seeds_from_mask_rows(L, m, fo_in, cb, sc, min_area, return_stats):
     return (init, fo, cl, stats, status) if return_stats else (init, fo, cl)
 
 
-def fit_ellipses_from_mask(mask, regions=DEFAULT_SEED_REGIONS, min_area=7, out=None):
+DEFAULT_RANSAC_REGIONS = ((0b110, 1, 0), (0b100, 2, 0b001))     # iris: boundary of classes 1 and 2 together; pupil: class 2 without
+                                                                # background-adjacent points (getValidPoints' condPupil)
+DEEPVOG_RANSAC_REGIONS = ((0, 1), (0b010, 1, 0))
+_ransac_cache = {}
+
+
+def _ransac_rows(regions, F, dev):
+    """_region_rows for region tuples that may carry a third element exclude_bits (default 0): (frame_of, class_bits, search_cls,
+    exclude_bits) [R*F] int32 on the device, cached like the seeds' tables."""
+    regions = tuple(tuple(int(v) for v in r) + (0,) * (3 - len(r)) for r in regions)
+    for r in regions:
+        if len(r) != 3 or not 0 <= r[2] < 1 << 32:
+            raise ValueError("regions: (class_bits, search_cls[, exclude_bits]) with bitmasks over class ids 0..31, got %r" % (r,))
+    fo, cb, sc = _region_rows(tuple(r[:2] for r in regions), F, dev)
+    key = (regions, int(F), str(dev))
+    if key not in _ransac_cache:
+        _ransac_cache[key] = torch.from_numpy(np.tile(np.array([r[2] for r in regions], dtype=np.uint32).view(np.int32), F)).to(dev)
+    return fo, cb, sc, _ransac_cache[key]
+
+
+def _draw_table(draws, n, K1, n_min, dev):
+    """An explicit draw table as an int32 device tensor.  A device tensor is used as it is (the form for a captured graph: nothing
+    is uploaded); anything else is uploaded by this call."""
+    d = draws if torch.is_tensor(draws) else torch.from_numpy(np.ascontiguousarray(np.asarray(draws, dtype=np.int32)))
+    d = d.to(device=dev, dtype=torch.int32).contiguous()
+    if tuple(d.shape) != (n, K1, n_min):
+        raise ValueError("draws: shape %r, expected [%d, %d, %d] (rows, iters + 1, n_min)" % (tuple(d.shape), n, K1, n_min))
+    return d
+
+
+def ellipse_ransac_from_mask(mask, regions=DEFAULT_RANSAC_REGIONS, n_min=15, iters=40, thres=5e-3, n_good=15, draws=None, seed=0,
+                             max_pts=4096, return_stats=False):
+    """The reference's ellipse estimator for masks on the device (csrc/ellifit.hip): per (frame, region) the boundary
+    points of the region, helperfunctions.ElliFit under helperfunctions.ransac(pts, ElliFit, n_min, iters, thres, n_good).loop().
+
+    mask [F,H,W] int64 class maps on the GPU; ``regions`` lists (class_bits, search_cls[, exclude_bits]) per frame in output order:
+    a pixel is in the region iff bit mask[p] of class_bits is set, and a boundary point is dropped when a pixel of its 3x3
+    neighbourhood has its bit set in exclude_bits.  ``draws``: None -- generated on the device from ``seed``, one stream per region, so
+    a frame's result does not depend on its place in the batch -- or an int32 table
+    [R*F, iters+1, n_min] of indices into each row's point list.  ``iters=-1``: the all-points fit only.  ``max_pts`` (even, at most
+    16384) caps a row's point list; a row with more is absent and sets status bit 1.
+    Returns (init [R*F,5] float64, frame_of [R*F] int32, cls [R*F] int32) on the device, the triple of ellipse_seeds_from_mask:
+    init is the fitted ellipse in the search's convention, absent rows are -1 five times with frame_of = -1.  With
+    ``return_stats`` also raw [R*F,5] (the reference's cx, cy, a, b, theta), stats_i int32 [R*F,4] (N, best iteration, inliers of the
+    best, candidates), stats_f float64 [R*F,2] (best error, my_ellipse(raw).verify(points)), the int32 status word (bit 0: a bad
+    draw, bit 1: more than max_pts points), points int16 [R*F,max_pts,2] (-1 past N) and the draws int32 [R*F,iters+1,n_min].
+    Nothing here synchronises; the estimator is the reference's, with its tight threshold: no robustness to occlusion is claimed."""
+    require_cuda(mask, "mask")
+    if mask.dtype != torch.int64 or mask.dim() != 3:
+        raise ValueError("mask must be an int64 [F,H,W] tensor")
+    L = _lib.lib()
+    dev = mask.device
+    F, H, W = (int(v) for v in mask.shape)
+    n_min, iters, n_good, max_pts = int(n_min), int(iters), int(n_good), int(max_pts)
+    if not (1 <= n_min <= 64 and -1 <= iters < 4096 and n_good >= 0):
+        raise ValueError("ellipse_ransac_from_mask: n_min 1..64, iters -1..4095, n_good >= 0")
+    fo_in, cb, sc, eb = _ransac_rows(DEFAULT_RANSAC_REGIONS if regions is None else regions, F, dev)
+    n = int(fo_in.shape[0])
+    nbytes = int(L.egne_ellipse_ransac_workspace_bytes(n, H, W, max_pts))
+    if nbytes < 0 or max_pts % 2:
+        raise ValueError("ellipse_ransac_from_mask: %d rows of %dx%d class maps, max_pts %d (2..1024 rows and columns, max_pts even and "
+                         "at most 16384)" % (n, H, W, max_pts))
+    K1 = iters + 1
+    table = None if draws is None else _draw_table(draws, n, K1, n_min, dev)
+    m = mask.contiguous()
+    ws = torch.empty((nbytes + 7) // 8, dtype=torch.int64, device=dev)
+    init = torch.empty((n, 5), dtype=torch.float64, device=dev)
+    raw = torch.empty((n, 5), dtype=torch.float64, device=dev)
+    fo = torch.empty((n,), dtype=torch.int32, device=dev)
+    cl = torch.empty((n,), dtype=torch.int32, device=dev)
+    stats_i = torch.empty((n, 4), dtype=torch.int32, device=dev)
+    stats_f = torch.empty((n, 2), dtype=torch.float64, device=dev)
+    status = torch.empty((1,), dtype=torch.int32, device=dev)
+    points = torch.full((n, max_pts, 2), -1, dtype=torch.int16, device=dev) if return_stats else None
+    draws_out = torch.empty((n, K1, n_min), dtype=torch.int32, device=dev) if (return_stats and table is None and K1 > 0) else None
+    _lib.check(L.egne_ellipse_ransac_from_mask(m.data_ptr(), F, fo_in.data_ptr(), cb.data_ptr(), sc.data_ptr(), eb.data_ptr(), n, H, W,
+                                               max_pts, n_min, iters, float(thres), n_good,
+                                               None if table is None else table.data_ptr(), int(seed) & 0xffffffff, n // F,
+                                               None if draws_out is None else draws_out.data_ptr(), raw.data_ptr(), init.data_ptr(),
+                                               fo.data_ptr(), cl.data_ptr(), stats_i.data_ptr(), stats_f.data_ptr(),
+                                               None if points is None else points.data_ptr(), status.data_ptr(), ws.data_ptr(),
+                                               _lib.stream_ptr()), "ellipse_ransac_from_mask")
+    if not return_stats:
+        return init, fo, cl
+    used = table if table is not None else (draws_out if draws_out is not None else torch.empty((n, 0, n_min), dtype=torch.int32, device=dev))
+    return init, fo, cl, raw, stats_i, stats_f, status, points, used
+
+
+def fit_ellipses_from_mask(mask, regions=None, min_area=7, out=None, seed_kind="mask", **ransac_args):
     """fit_ellipses_from_pred with the seeds of ellipse_seeds_from_mask: seeds, then every search in one launch on the same stream.
     Returns a DEVICE tensor [F,R,5] float64, region order as in ``regions`` (default: iris, pupil); absent rows are -1 five times
-    (the search reports NaN for them; a device-side select puts the seed's -1 back).  Nothing here synchronises."""
-    init, fo, cl = ellipse_seeds_from_mask(mask, regions, min_area)
+    (the search reports NaN for them; a device-side select puts the seed's -1 back).  Nothing here synchronises.
+    ``regions=None``: the default regions of the seed kind.  ``seed_kind="ransac"``: the seeds are those of
+    ellipse_ransac_from_mask(mask, regions, **ransac_args); min_area is not used."""
+    if seed_kind == "ransac":
+        init, fo, cl = ellipse_ransac_from_mask(mask, regions, **ransac_args)
+    elif seed_kind == "mask":
+        if ransac_args:
+            raise TypeError("fit_ellipses_from_mask: %r only with seed_kind='ransac'" % (sorted(ransac_args),))
+        init, fo, cl = ellipse_seeds_from_mask(mask, regions, min_area)
+    else:
+        raise ValueError("fit_ellipses_from_mask: seed_kind %r (mask or ransac)" % (seed_kind,))
     L = _lib.lib()
     F, H, W = mask.shape
     R = init.shape[0] // F

@@ -709,6 +709,41 @@ int egne_ellipse_init_from_mask(const int64_t* mask, int nframes, const int32_t*
                                 int32_t* out_frame_of, int32_t* out_cls, int64_t* stats, int32_t* status, void* ws,
                                 void* stream);
 
+/*
+ * Ellipses from class-map boundaries (csrc/ellifit.hip): the reference's helperfunctions.ElliFit (:209-276) under
+ * helperfunctions.ransac (:278-310), the estimator behind its dataset_generation/Extract*.py "Fits", per (frame, region) row on the
+ * device -- it replaces ransac(pts, ElliFit, n_min, iters, thres, n_good).loop() and my_ellipse(model).verify(pts) on the host.
+ * Rows as for egne_ellipse_init_from_mask plus exclude_bits[i].  Boundary point: in the region, at least one 4-neighbour inside
+ * the image outside the region, no pixel of its 3x3 neighbourhood inside the image with its bit set in exclude_bits (class ids
+ * outside 0..31 neither belong nor exclude); (x, y) = (column, row) in raster order, at most max_pts (even, <= 16384) of them --
+ * a row with more is absent and sets bit 1 of `status`.  Fit(S): float64, centred on S's mean, normal equations of
+ * X = [x^2, 2xy, -2x, -2y, -1], Y = -y^2 by Cholesky, model = lines :249-257; a singular system or a non-finite entry makes the
+ * model invalid, its error +inf.  Candidate -1 = Fit(all); for N > n_min iterations i = 0..iters: S_i (n_min distinct indices),
+ * I = S_i u {p : fit_error(Fit(S_i), p) < thres}, candidate i = Fit(I) iff |I| > max(n_good, n_min), error = mean fit_error over
+ * I; result = smallest (error, i).  iters = -1: candidate -1 only.  Fewer than 7 points: absent.
+ * draws: int32 [n][iters+1][n_min] indices into the row's point list (an index outside [0, N) or a repeated one sets bit 0 of
+ * `status` and makes the row absent), or NULL: generated from `seed` -- attempt t of iteration i of row r is
+ * mulhi(hash(seed, r % draw_period, i, t), N), indices already taken are skipped, at most 256 attempts (then bit 0); with
+ * draw_period = rows per frame a frame's ellipses do not depend on where in a batch, or in how large a batch, the frame sits
+ * (draw_period = n: every row its own stream).  draws_out (may be NULL) receives them, -1 where a row ran no iteration or an
+ * iteration's attempts ran out.
+ * Outputs per row: raw [n][5] the reference's (cx, cy, a, b, theta); init [n][5] the same ellipse as the search reads it (centre
+ * and second-moment form scaled by W/(W-1), H/(H-1), a the semi-axis along theta); out_frame_of / out_cls as the mask seeds (-1
+ * and five times -1 where absent); stats_i [n][4] = (N, best iteration, |I| of the best, candidates including -1); stats_f [n][2]
+ * = (best error, mean of p^T M p over all points, M = my_ellipse(raw).mat); points_out (may be NULL) int16 [n][max_pts][2], only
+ * the first N entries of a row are written.  ws: egne_ellipse_ransac_workspace_bytes(n, H, W, max_pts) bytes (negative for
+ * refused sizes: H, W outside 2..1024, max_pts outside 1..16384), aligned to 8.  Five launches on `stream`, fixed sequence
+ * (capturable): ballot words, their prefix, the point list, one workgroup of four waves per row for the fits (max_pts*4 + 1552
+ * bytes of LDS), one thread per row for the outputs; no host synchronisation, no allocation.
+ */
+int64_t egne_ellipse_ransac_workspace_bytes(int n, int H, int W, int max_pts);
+int egne_ellipse_ransac_from_mask(const int64_t* mask, int nframes, const int32_t* frame_of, const int32_t* class_bits,
+                                  const int32_t* search_cls, const int32_t* exclude_bits, int n, int H, int W, int max_pts,
+                                  int n_min, int iters, double thres, int n_good, const int32_t* draws, uint32_t seed,
+                                  int draw_period, int32_t* draws_out, double* raw, double* init, int32_t* out_frame_of, int32_t* out_cls,
+                                  int32_t* stats_i, double* stats_f, int16_t* points_out, int32_t* status, void* ws,
+                                  void* stream);
+
 /* Device-side batch preparation (the reference does this per sample on the host in its Dataset).
  * egne_dist_maps: out[b][c] = helperfunctions.one_hot2dist(label[b] == c) (helperfunctions.py:356-371, called from
  *   CurriculumLib.py:131-136): signed exact Euclidean distance transform normalised by the image diagonal, 0 for an absent
