@@ -18,11 +18,22 @@
 //   producers (waves 0-3)  halo gather (two jobs of loads in flight), optional fused InstanceNorm affine + activation, fp32 ->
 //             hi / lo with plain VALU (split_f16.h), image (job + 1) & 1;
 //   consumers (waves 4-7)  two rows x 32 channels each on v_mfma_f32_16x16x32_f16 (eight independent accumulators): 9 taps x 24
-//             MFMAs per job, operands of tap t + 1 requested before the MFMAs of tap t; transposed product, so a lane ends with 16 channels of one pixel: 8 stores of 16 bytes per tile,
+//             MFMAs per job, operands of tap t + 1 requested among the MFMAs of tap t; transposed product, so a lane ends with 16 channels of one pixel: 8 stores of 16 bytes per tile,
 //             issued between the MFMAs of the next job; optional second output = 2x2 ceil-mode max pooling (pool1 of conv1_2).
 // One s_barrier per job.
+//
+// Two forms of the consumer loop (template parameter SH, same MFMA order and epilogue arithmetic: bit-identical results,
+// tests/test_gpu_rw_shadow.py).  The consumer is the only MFMA-issuing wave of its SIMD, so every vector instruction it issues outside
+// an MFMA's shadow idles the matrix pipe.  Hand-over form (SH = 0, EGNE_RW_SHADOW=0): a finished tile is copied to a second register
+// set, scaled / activated / pooled there and its next tile's coordinates decoded BETWEEN two tiles (~880 of 7 000 cycles per
+// three-product job, 1 280 of 4 100 with one product), the taps request their operands in one burst.  Shadow form (default): the two
+// register sets swap roles by tile parity, the finished tile's groups are finished and stored among the MFMAs of the next tile's
+// first job, the tile coordinates advance without a division, and a tap's reads and vector instructions sit between its MFMAs
+// (sched_group_barrier; the ISA of a tap is M d v v v M d v v v ...).  Three products, 64 -> 64 at 240x320x64: 1.23 -> 1.03 ms, a
+// consumer's work per job 7 000 -> 4 610 cycles against 3 456 of MFMA issue -- and level with the producers' 4 700, which now co-limit.
 #include "common.h"
 #include "split_f16.h"
+#include <cstdlib>
 #include <type_traits>
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
@@ -60,7 +71,11 @@ __device__ __forceinline__ void lds_barrier() {
 // halves are neither derived, stored nor read; the frozen edge network next to a bf16-storage training plan)
 // F16IN: the input slice is held as f16 (egne_seg.presplit = 2: plain halves of x * a_scale in channel order, written by a producer with
 // egne_conv_desc.out_split = 2): a producer item is a 16-byte copy of eight channels, no conversion (NP = 1 only)
-template <int KCH, int NP = 3, bool F16IN = false>
+// SH: form of the consumer loop.  0 = the hand-over form (all of a tile's epilogue between its last job and the next tile's first;
+// EGNE_RW_SHADOW=0), 1-4 = the shadow form (below) with the epilogue options read at run time (1) or fixed at compile time so that a
+// tap stays ONE basic block: 2 = fp32 store, 3 = fp32 store + pooled second output, 4 = split-pair store (no post affine / residual),
+// 5 = fp32 store behind a post affine and / or a residual (which of the two: read at run time).
+template <int KCH, int NP = 3, bool F16IN = false, int SH = 0>
 __global__ __launch_bounds__(512)
 void conv3x3_rw_kernel(const egne_conv_desc p, const _Float16* __restrict__ fhi, const _Float16* __restrict__ flo, float a_scale,
                        float out_scale, int tiles_x, int tiles_y, int ntiles, int ncb, int nrun) {
@@ -69,7 +84,7 @@ void conv3x3_rw_kernel(const egne_conv_desc p, const _Float16* __restrict__ fhi,
   _Float16* const lw = ldsh + 2 * IMGH;                  // weights behind the two images
 
   const int dbg = g_wdbg;
-  unsigned long long t_work = 0, t_wait = 0, t_last = 0;
+  unsigned long long t_work = 0, t_wait = 0, t_hand = 0, t_last = 0;
   auto stamp = [&](unsigned long long& accum) {
     if (dbg & 64) {
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
@@ -273,6 +288,264 @@ void conv3x3_rw_kernel(const egne_conv_desc p, const _Float16* __restrict__ fhi,
       step(s + 1, B0{});
       stamp(t_work); lds_barrier(); stamp(t_wait);
     }
+  } else if constexpr (SH != 0) {
+    // =================================================================== consumers, shadow form: the same MFMAs per accumulator in the
+    // same order and the same epilogue arithmetic as the hand-over form below (which documents both), but nothing is done BETWEEN tiles:
+    //   * two accumulator sets that swap roles by tile parity (the tile loop is unrolled by two): a tile's first MFMA per accumulator
+    //     takes a zero C operand, the finished tile stays where it is -- no copies, no zeroing;
+    //   * group g of the finished tile (its pooled part first) is finished in place and stored among the MFMAs of tap g of the next
+    //     tile's first job; its addresses are built there from the finished tile's scalar coordinates and lane constants (no offset
+    //     registers carried); the first tile of a workgroup "finishes" a set of zeros into a resource of zero bytes;
+    //   * the tile coordinates advance by nworkers tiles without a division;
+    //   * the ds_read_b128 of tap t + 1 and the epilogue's vector instructions are placed between the MFMAs of tap t
+    //     (sched_group_barrier: one read and up to three vector instructions behind each MFMA).
+    constexpr bool GEN = SH == 1;
+    const int cw = wave - 4, row0 = cw * 2;
+    const int l15 = lane & 15, kg = lane >> 4;
+    const bool o16 = GEN && NP == 1 && p.out_split == 2;
+    const bool split_on = SH == 4 || (GEN && !o16 && p.out_split != 0);
+    const bool pool_on = SH == 3 || (GEN && p.pool_out != nullptr);
+    const bool full_epi = SH == 5 || (GEN && (p.post_scale != nullptr || p.residual != nullptr));
+    const int oesz = o16 ? 2 : 4;
+    const unsigned frame_out = (unsigned)H * W * (unsigned)p.out_pix_stride * (unsigned)oesz;
+    const unsigned frame_res = (unsigned)H * W * (unsigned)p.res_pix_stride * 4u;
+    const int Hp = (H + 1) >> 1, Wp = (W + 1) >> 1;
+    const unsigned frame_pool = (unsigned)Hp * Wp * (unsigned)p.pool_pix_stride * (unsigned)oesz;
+    const float slope_out = p.act == EGNE_ACT_RELU ? 0.f : (p.act == EGNE_ACT_LEAKY ? 0.01f : 1.f);
+    f32x4 b4[2];
+    bool jok[2];
+#pragma unroll
+    for (int nh = 0; nh < 2; ++nh) {
+      const int n = cb * 32 + nh * 16 + 4 * kg;
+      b4[nh] = p.bias ? *(const f32x4*)(p.bias + n) : (f32x4)(0.f);
+      jok[nh] = n < p.Cout_store;
+    }
+    int aofs[9][2][2];
+#pragma unroll
+    for (int tap = 0; tap < 9; ++tap)
+#pragma unroll
+      for (int tm = 0; tm < 2; ++tm)
+#pragma unroll
+        for (int ph = 0; ph < 2; ++ph) {
+          const int qq = (row0 + tm + tap / 3) * HWd + ph * 16 + l15 + tap % 3;
+          aofs[tap][tm][ph] = qq * 32 + ((kg ^ ((qq >> 1) & 3)) << 3);
+        }
+    const int wl = (kg >> 1) * 1024 + ((kg & 1) * 32 + l15) * 8;
+    // lane constants of the store addresses: byte offset of (pixel column 16 ph + l15, first channel of the lane) in a tile row; the
+    // tile's part ((y W + x0) pixels) is wave-uniform and added at the tap that stores
+    int xl[2], xlp[2], lco[2], lcr[2], lcp[2];
+#pragma unroll
+    for (int ph = 0; ph < 2; ++ph) {
+      xl[ph] = ph * 16 + l15;
+      xlp[ph] = (l15 & 1) ? 0x40000000 : xl[ph];       // (the pooled store: even columns only)
+      lco[ph] = (xl[ph] * (int)p.out_pix_stride + p.out_ch_off + cb * 32 + 4 * kg) * oesz;
+      lcr[ph] = (xl[ph] * (int)p.res_pix_stride + p.res_ch_off + cb * 32 + 4 * kg) * 4;
+      lcp[ph] = ((xl[ph] >> 1) * (int)p.pool_pix_stride + p.pool_ch_off + cb * 32 + 4 * kg) * oesz;
+    }
+    f32x4 R[2][2][2][2];                                 // [set][tm][ph][nh]: tile i accumulates in set i & 1
+#pragma unroll
+    for (int a = 0; a < 16; ++a) (&R[0][0][0][0])[a] = (f32x4)(0.f);
+    // the finished tile (wave-uniform): frame resources, first row of this wave, first column; nothing yet: resources of zero bytes
+    __amdgpu_buffer_rsrc_t rout = make_rsrc(p.out, 0u), rres = make_rsrc(nullptr, 0u), rpo = make_rsrc(nullptr, 0u);
+    // ... and its wave-uniform address parts, per row tm of the wave: columns of the tile inside the image (0: the row is outside it),
+    // byte offset of the row's first pixel in the output / residual frame; the same for the pooled row
+    int wlim[2] = {0, 0}, sbo[2] = {0, 0}, sbr[2] = {0, 0}, wlim_p = 0, x1lim = 0, sbp = 0;
+    bool y1 = false;
+    bool have_prev = false;
+    // overflow word: the largest |bits| of the tested values, on the vector ALU alone (a compare into a scalar pair and two scalar
+    // instructions per group would sit between the MFMAs); non-finite = at or above the bits of infinity, tested once at the end
+    unsigned ovf_m = 0u, ovf_h = 0u;
+    int tvo = (int)OOB, tvr = (int)OOB, poff = (int)OOB;   // addresses of the group pair (tm, ph), built at its even tap
+    // everything group Gi of the finished tile (register set Q) still needs
+    auto epi = [&](auto qc, auto gc) {
+      constexpr int Q = decltype(qc)::value, Gi = decltype(gc)::value, nh = Gi & 1, ph = (Gi >> 1) & 1, tm = Gi >> 2;
+      // guards as one vector compare each: column 16 ph + l15 against the tile's columns inside the image (none for a row outside it)
+      if constexpr (tm == 0) {
+        if (pool_on) {                                   // pooled part of (ph, nh): reads both rows BEFORE either is finished in place
+          const bool x1 = xl[ph] < x1lim;
+          if constexpr (nh == 0) poff = xlp[ph] < wlim_p ? lcp[ph] + sbp : (int)OOB;
+          f32x4 v;
+#pragma unroll
+          for (int e = 0; e < 4; ++e) {
+            float m = R[Q][0][ph][nh][e];
+            m = y1 ? fmaxf(m, R[Q][1][ph][nh][e]) : m;
+            const float qn = __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, m), 0xB1, 0xf, 0xf, false));   // lane ^ 1
+            m = x1 ? fmaxf(m, qn) : m;
+            const float t = m * out_scale + b4[nh][e];
+            v[e] = fmaxf(t, t * slope_out);
+          }
+          if (o16) {
+            const egne::sp_f32x2 u0 = {v[0] * p.out_split_scale, v[1] * p.out_split_scale}, u1 = {v[2] * p.out_split_scale, v[3] * p.out_split_scale};
+            const h2 h0 = __builtin_convertvector(u0, h2), h1 = __builtin_convertvector(u1, h2);
+            const u32x2 two = {__builtin_bit_cast(unsigned, h0), __builtin_bit_cast(unsigned, h1)};
+            __builtin_amdgcn_raw_buffer_store_b64(two, rpo, jok[nh] ? poff : (int)OOB, nh * 32, 0);
+          } else {
+            __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), rpo, jok[nh] ? poff : (int)OOB, nh * 64, 0);
+          }
+        }
+      }
+      if constexpr (nh == 0) {
+        const bool okp = xl[ph] < wlim[tm];
+        tvo = okp ? lco[ph] + sbo[tm] : (int)OOB;
+        if (full_epi) tvr = okp ? lcr[ph] + sbr[tm] : (int)OOB;
+      }
+      f32x4 v;
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        const float t = R[Q][tm][ph][nh][e] * out_scale + b4[nh][e];
+        v[e] = fmaxf(t, t * slope_out);
+      }
+      if (full_epi) {
+        const int n = cb * 32 + nh * 16 + 4 * kg;
+        if (p.post_scale) {
+          const f32x4 ps = *(const f32x4*)(p.post_scale + n), pt = *(const f32x4*)(p.post_shift + n);
+#pragma unroll
+          for (int e = 0; e < 4; ++e) v[e] = v[e] * ps[e] + pt[e];
+        }
+        if (p.residual) {
+          const f32x4 rv = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rres, jok[nh] ? tvr : (int)OOB, nh * 64, 0));
+#pragma unroll
+          for (int e = 0; e < 4; ++e) v[e] += rv[e];
+        }
+      }
+      if constexpr (nh == 0) ovf_m = max(ovf_m, __builtin_bit_cast(unsigned, v[0]) & 0x7fffffffu);
+      if (o16) {
+        const egne::sp_f32x2 u0 = {v[0] * p.out_split_scale, v[1] * p.out_split_scale}, u1 = {v[2] * p.out_split_scale, v[3] * p.out_split_scale};
+        const h2 h0 = __builtin_convertvector(u0, h2), h1 = __builtin_convertvector(u1, h2);
+        if constexpr (nh == 0) ovf_h = max(ovf_h, __builtin_bit_cast(unsigned, h0) & 0x7fffu);
+        const u32x2 two = {__builtin_bit_cast(unsigned, h0), __builtin_bit_cast(unsigned, h1)};
+        __builtin_amdgcn_raw_buffer_store_b64(two, rout, jok[nh] ? tvo : (int)OOB, nh * 32, 0);
+      } else if (split_on) {
+        h2 h0, h1, l0, l1;
+        egne::split2(v[0], v[1], p.out_split_scale, h0, l0);
+        egne::split2(v[2], v[3], p.out_split_scale, h1, l1);
+        const u32x4 pk = {__builtin_bit_cast(unsigned, h0), __builtin_bit_cast(unsigned, h1), __builtin_bit_cast(unsigned, l0), __builtin_bit_cast(unsigned, l1)};
+        R[Q][tm][ph][nh] = __builtin_bit_cast(f32x4, pk);     // (the halves of nh = 0 wait one tap for their neighbours)
+        if constexpr (nh == 1) {
+          const u32x4 p0 = __builtin_bit_cast(u32x4, R[Q][tm][ph][0]), p1 = __builtin_bit_cast(u32x4, R[Q][tm][ph][1]);
+          const u32x4 hi = {p0[0], p0[1], p1[0], p1[1]}, lo = {p0[2], p0[3], p1[2], p1[3]};
+          __builtin_amdgcn_raw_buffer_store_b128(hi, rout, tvo, 0, 0);
+          if constexpr (NP == 3) __builtin_amdgcn_raw_buffer_store_b128(lo, rout, tvo, 64, 0);
+        }
+      } else {
+        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), rout, jok[nh] ? tvo : (int)OOB, nh * 64, 0);
+      }
+    };
+    // tile coordinates: tile worker + i nworkers as (frame, tile row, tile column), advanced with carries
+    const int d_tx = nworkers % tiles_x, d_ty = (nworkers / tiles_x) % tiles_y, d_b = (nworkers / tiles_x) / tiles_y;
+    int tx = worker % tiles_x, ty = (worker / tiles_x) % tiles_y, tb = (worker / tiles_x) / tiles_y;
+    int s = 0;                                           // job counter: LDS image (and streamed weight buffer) s & 1
+    // one job: FIRST = chunk 0 of a tile (zero C operand at tap 0, the finished tile's groups at taps 0-7)
+    auto job = [&](auto pc, auto fc, int ch) {
+      constexpr int P = decltype(pc)::value;
+      constexpr bool FIRST = decltype(fc)::value;
+      const _Float16* Thi = ldsh + (s & 1) * IMGH;
+      const _Float16* Tlo = Thi + NPX * 32;
+      const _Float16* wb = lw + (STREAM ? (s & 1) : ch) * WCH + wl;
+      h8 wh[2][2], wo[2][2], ah[2][2][2], al[2][2][2];
+      auto fetch = [&](auto tc) {
+        constexpr int T = decltype(tc)::value, Bq = T & 1;
+#pragma unroll
+        for (int nh = 0; nh < 2; ++nh) {
+          wh[Bq][nh] = *(const h8*)&wb[T * 2048 + nh * 128];
+          if constexpr (NP == 3) wo[Bq][nh] = *(const h8*)&wb[T * 2048 + 512 + nh * 128];
+        }
+#pragma unroll
+        for (int tm = 0; tm < 2; ++tm)
+#pragma unroll
+          for (int ph = 0; ph < 2; ++ph) {
+            ah[Bq][tm][ph] = *(const h8*)&Thi[aofs[T][tm][ph]];
+            if constexpr (NP == 3) al[Bq][tm][ph] = *(const h8*)&Tlo[aofs[T][tm][ph]];
+          }
+      };
+      fetch(std::integral_constant<int, 0>{});
+      [&]<int... Ts>(std::integer_sequence<int, Ts...>) {
+        (([&] {
+          constexpr int t = Ts, Bq = t & 1;
+          __builtin_amdgcn_sched_barrier(0);
+          if constexpr (t + 1 < 9) fetch(std::integral_constant<int, t + 1>{});
+          if constexpr (FIRST && t < 8) epi(std::integral_constant<int, P ^ 1>{}, std::integral_constant<int, t>{});
+#pragma unroll
+          for (int tm = 0; tm < 2; ++tm)
+#pragma unroll
+            for (int ph = 0; ph < 2; ++ph)
+#pragma unroll
+              for (int nh = 0; nh < 2; ++nh) {
+                f32x4 c = R[P][tm][ph][nh];
+                if constexpr (FIRST && t == 0) c = (f32x4)(0.f);
+                if constexpr (NP == 3) {
+                  c = __builtin_amdgcn_mfma_f32_16x16x32_f16(wh[Bq][nh], al[Bq][tm][ph], c, 0, 0, 0);
+                  c = __builtin_amdgcn_mfma_f32_16x16x32_f16(wo[Bq][nh], ah[Bq][tm][ph], c, 0, 0, 0);
+                }
+                c = __builtin_amdgcn_mfma_f32_16x16x32_f16(wh[Bq][nh], ah[Bq][tm][ph], c, 0, 0, 0);
+                R[P][tm][ph][nh] = c;
+              }
+          // placement: behind each MFMA one operand read of the next tap and up to three vector instructions (four in the taps that
+          // carry a pooled group); the stores behind the last MFMAs (a store slot in mid-tap pulls everything it depends on in front
+          // of it in one burst)
+          constexpr int NM = NP == 3 ? 24 : 8, ND = t + 1 < 9 ? (NP == 3 ? 12 : 6) : 0, NV = FIRST && SH == 3 && t < 4 ? 4 : 3;
+          [&]<int... Ms>(std::integer_sequence<int, Ms...>) {
+            (([&] {
+              __builtin_amdgcn_sched_group_barrier(0x8, 1, 0);
+              if constexpr (Ms < ND) __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
+              __builtin_amdgcn_sched_group_barrier(0x2, NV, 0);
+              if constexpr (FIRST && Ms >= NM - 3) __builtin_amdgcn_sched_group_barrier(0x40, 1, 0);
+            }()), ...);
+          }(std::make_integer_sequence<int, NM>{});
+        }()), ...);
+      }(std::make_integer_sequence<int, 9>{});
+      __builtin_amdgcn_sched_barrier(0);
+      ++s;
+      stamp(t_work); lds_barrier(); stamp(t_wait);
+    };
+    auto tile = [&](auto pc) {
+      job(pc, std::true_type{}, 0);
+      for (int ch = 1; ch < nk; ++ch) job(pc, std::false_type{}, ch);
+      // the tile is finished: its coordinates for the next tile's first job (scalar unit only), then the next tile's
+      const int py = ty * TH + row0, px = tx * TW;
+#pragma unroll
+      for (int tm = 0; tm < 2; ++tm) {
+        const bool in = py + tm < H;                     // (a row below the image has no offset: the product could leave int)
+        wlim[tm] = in ? W - px : 0;
+        sbo[tm] = in ? ((py + tm) * W + px) * (int)p.out_pix_stride * oesz : 0;
+        if (full_epi) sbr[tm] = in ? ((py + tm) * W + px) * (int)p.res_pix_stride * 4 : 0;
+      }
+      if (pool_on) {
+        y1 = py + 1 < H; x1lim = W - px - 1; wlim_p = wlim[0];
+        sbp = py < H ? ((py >> 1) * Wp + (px >> 1)) * (int)p.pool_pix_stride * oesz : 0;
+      }
+      rout = make_rsrc((char*)p.out + (long long)tb * H * W * p.out_pix_stride * oesz, frame_out);
+      if (full_epi) rres = make_rsrc(p.residual ? p.residual + (long long)tb * H * W * p.res_pix_stride : nullptr, p.residual ? frame_res : 0u);
+      if (pool_on) rpo = make_rsrc((char*)p.pool_out + (long long)tb * Hp * Wp * p.pool_pix_stride * oesz, frame_pool);
+      if (!have_prev) ovf_m = ovf_h = 0u;                // (the first tile of a workgroup finished a set of zeros)
+      have_prev = true;
+      tx += d_tx;
+      int c = tx >= tiles_x ? 1 : 0;
+      tx -= c ? tiles_x : 0;
+      ty += d_ty + c;
+      c = ty >= tiles_y ? 1 : 0;
+      ty -= c ? tiles_y : 0;
+      tb += d_b + c;
+    };
+    using P0 = std::integral_constant<int, 0>;
+    using P1 = std::integral_constant<int, 1>;
+    lds_barrier();
+    t_last = __builtin_amdgcn_s_memtime();
+    for (int i = 0; i < ntl; i += 2) {
+      tile(P0{});
+      if (i + 1 < ntl) tile(P1{});
+    }
+    if (nmine & 1) { stamp(t_work); lds_barrier(); stamp(t_wait); }      // (both roles run an even number of steps)
+    stamp(t_work);
+    if (have_prev) {                                     // the last tile's groups
+      auto flush = [&](auto qc) {
+        [&]<int... Gs>(std::integer_sequence<int, Gs...>) { (epi(qc, std::integral_constant<int, Gs>{}), ...); }(std::make_integer_sequence<int, 8>{});
+      };
+      if (ntl & 1) flush(P0{}); else flush(P1{});
+    }
+    stamp(t_hand);
+    const bool ovf_bad = egne_nonfinite(__builtin_bit_cast(float, ovf_m)) || egne_nonfinite((float)__builtin_bit_cast(_Float16, (unsigned short)ovf_h));
+    egne_ovf_commit(ovf_bad, p.ovf_flag);
   } else {
     // =================================================================== consumers: 9 taps per job from LDS only
     // v_mfma_f32_16x16x32_f16: one instruction per (16 channels, 16 pixels, 32 input channels of a tap); a wave's two rows x 32
@@ -438,6 +711,7 @@ void conv3x3_rw_kernel(const egne_conv_desc p, const _Float16* __restrict__ fhi,
           }()), ...);
         }(std::make_integer_sequence<int, 9>{});
         if (ch == nk - 1) {                                // tile complete: hand it to the deferred stores
+          stamp(t_work);
           const int y = tl.y0 + row0;
           if (p.pool_out) {      // second output: 2x2 / stride 2 / ceil-mode max pooling (act(max) = max(act): monotonic activation)
             const int Hp = (H + 1) >> 1, Wp = (W + 1) >> 1;
@@ -487,6 +761,7 @@ void conv3x3_rw_kernel(const egne_conv_desc p, const _Float16* __restrict__ fhi,
             }
           [&]<int... Gs>(std::integer_sequence<int, Gs...>) { (finish_group(std::integral_constant<int, Gs>{}), ...); }(std::make_integer_sequence<int, 8>{});
           have_prev = true;
+          stamp(t_hand);
         }
       }
       stamp(t_work); lds_barrier(); stamp(t_wait);
@@ -497,20 +772,43 @@ void conv3x3_rw_kernel(const egne_conv_desc p, const _Float16* __restrict__ fhi,
   }
   if ((dbg & 64) && lane == 0) {
     unsigned long long* o = g_wstamps + ((long long)blockIdx.x * 8 + wave) * 4;
-    o[0] = t_work; o[1] = t_wait; o[2] = nmine; o[3] = 0;
+    o[0] = t_work + t_hand; o[1] = t_wait; o[2] = nmine; o[3] = t_hand;      // (consumers: [3] = the part of [0] outside the tap loops)
   }
 }
 
+template <int KCH, int NP, bool F16IN, int SH>
+int launch_rw_form(const egne_conv_desc& d, const _Float16* fhi, const _Float16* flo, float a_scale, float os, hipStream_t st);
+
+// The form of the consumer loop (template parameter SH of the kernel).  EGNE_RW_SHADOW=0, read at every launch, keeps the hand-over
+// form: the tests compare the two inside one process (they agree bit for bit).  The three-product kernels fix the epilogue at
+// compile time (read at run time it does not fit next to 96 operand registers: it spilled); only a pooled output TOGETHER with a
+// post affine or a residual, which no layer of the networks has, keeps the hand-over form.  The one-product kernels read the
+// epilogue at run time.
 template <int KCH, int NP = 3, bool F16IN = false>
 int launch_rw(const egne_conv_desc& d, const _Float16* fhi, const _Float16* flo, float a_scale, float os, hipStream_t st) {
+  const char* e = getenv("EGNE_RW_SHADOW");
+  if (e && e[0] == '0') return launch_rw_form<KCH, NP, F16IN, 0>(d, fhi, flo, a_scale, os, st);
+  if constexpr (NP == 3) {
+    if ((d.post_scale || d.residual) && d.pool_out) return launch_rw_form<KCH, NP, F16IN, 0>(d, fhi, flo, a_scale, os, st);
+    if (d.post_scale || d.residual) return launch_rw_form<KCH, NP, F16IN, 5>(d, fhi, flo, a_scale, os, st);
+    if (d.pool_out) return launch_rw_form<KCH, NP, F16IN, 3>(d, fhi, flo, a_scale, os, st);
+    if (d.out_split) return launch_rw_form<KCH, NP, F16IN, 4>(d, fhi, flo, a_scale, os, st);
+    return launch_rw_form<KCH, NP, F16IN, 2>(d, fhi, flo, a_scale, os, st);
+  } else {
+    return launch_rw_form<KCH, NP, F16IN, 1>(d, fhi, flo, a_scale, os, st);
+  }
+}
+
+template <int KCH, int NP, bool F16IN, int SH>
+int launch_rw_form(const egne_conv_desc& d, const _Float16* fhi, const _Float16* flo, float a_scale, float os, hipStream_t st) {
   const int tiles_x = (d.W + TW - 1) / TW, tiles_y = (d.H + TH - 1) / TH;
   const int ntiles = tiles_x * tiles_y * d.B, ncb = d.CoutP / 32, nrun = (d.Cout_store + 31) / 32;
   constexpr size_t lds = ((size_t)2 * IMGH + (size_t)(KCH == 0 ? 2 : KCH) * WCH) * sizeof(_Float16);
   static_assert(lds <= 163840, "LDS budget");
-  static bool once = hipFuncSetAttribute((const void*)conv3x3_rw_kernel<KCH, NP, F16IN>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) == hipSuccess;
+  static bool once = hipFuncSetAttribute((const void*)conv3x3_rw_kernel<KCH, NP, F16IN, SH>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) == hipSuccess;
   if (!once) return egne::fail(EGNE_ERR_LAUNCH, "conv3x3_rw: cannot raise the dynamic LDS limit to %zu", lds);
   // 256 workgroups = 8 XCDs x 32; the ncb blocks of a worker sit on one XCD: 32 / ncb workers per XCD
-  hipLaunchKernelGGL((conv3x3_rw_kernel<KCH, NP, F16IN>), dim3(256), dim3(512), lds, st, d, fhi, flo, a_scale, os, tiles_x, tiles_y, ntiles, ncb, nrun);
+  hipLaunchKernelGGL((conv3x3_rw_kernel<KCH, NP, F16IN, SH>), dim3(256), dim3(512), lds, st, d, fhi, flo, a_scale, os, tiles_x, tiles_y, ntiles, ncb, nrun);
   return egne::check_launch("egne_conv3x3_rw_f16_fwd");
 }
 
