@@ -1,8 +1,7 @@
 // AdaIN fusion path of ESF-Net (models/RITnet_v2.py:289-308, calc_mean_std :251-259) and the
 // dataset-confusion loss (loss.py:139-157, models/RITnet_v2.py:343-350).  Small HBM-bound kernels.
 #include "common.h"
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
+#include "kernel_util.h"
 
 namespace {
 

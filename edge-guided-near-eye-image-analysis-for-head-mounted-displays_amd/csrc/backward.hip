@@ -4,10 +4,8 @@
 // and the HBM-bound elementwise / reduction backward ops.  Everything is deterministic (two-stage
 // reductions, no atomics).
 #include "common.h"
+#include "kernel_util.h"
 #include <type_traits>
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 namespace {
 

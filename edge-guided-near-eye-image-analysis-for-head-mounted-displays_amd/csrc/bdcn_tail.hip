@@ -1,8 +1,7 @@
 // BDCN side-output path (bdcn_new.py:118-191): per-stage 1x1 "down" convs + score heads, then the
 // transposed-conv upsampling / crop / cascades / fuse / sigmoid tail.  HBM-bound byte work.
 #include "common.h"
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
+#include "kernel_util.h"
 
 namespace {
 

@@ -99,7 +99,7 @@ template <typename T> __device__ __forceinline__ const T* zero_page() { return (
 // zero included).  So a kernel whose lanes hold pixels tests ONE channel per pixel, and a kernel whose lanes hold channels and
 // whose registers walk the pixels of an image row tests the rows y % 3 == 1 and the last row of a 3x3 / dilation-1 convolution
 // (any three consecutive rows, clipped to the image, contain one of them) -- egne_ovf_row.
-#ifdef EGNE_NO_OVF_CHECK      // (A/B builds only: what the tests cost, scratch/ab_ovf.sh)
+#ifdef EGNE_NO_OVF_CHECK      // (A/B builds only, make OBJDIR=... EXTRA_CXXFLAGS=-DEGNE_NO_OVF_CHECK: what the tests cost, scratch/ab_ovf.sh)
 __device__ __forceinline__ bool egne_nonfinite(float) { return false; }
 __device__ __forceinline__ bool egne_nonfinite64(double) { return false; }
 #else
@@ -153,6 +153,8 @@ inline bool raise_lds(const void* kern, size_t bytes) {
   have[kern] = bytes;
   return true;
 }
+// the same limit for every kernel an entry point chooses between
+template <typename... K> inline bool raise_lds_all(size_t bytes, K... kern) { return (raise_lds((const void*)kern, bytes) && ...); }
 
 #define EGNE_REQUIRE(cond, ...) \
   do { if (!(cond)) return ::egne::fail(EGNE_ERR_ARG, __VA_ARGS__); } while (0)
@@ -171,17 +173,6 @@ int wgrad3x3_bf16_launch(const egne_conv_desc& d, const egne_bf16* gz, long long
 bool wgrad1x1_bf16_supported(const egne_conv_desc& d, long long gzs);   // 1x1 over raw bf16 slices, all block pairs in one workgroup
 int wgrad1x1_bf16_splits(const egne_conv_desc& d);
 int wgrad1x1_bf16_launch(const egne_conv_desc& d, const egne_bf16* gz, long long gzs, int gzo, float* ws, hipStream_t st);
-
-int msdil_ps_launch(const egne_conv_desc& d, const void* fhi, const void* flo, float a_scale, float w_scale, const float* score_w,
-                    const float* score_c, float* s0, float* s1, int accumulate, hipStream_t st);   // msblock_dil_ps_f16.hip
-
-bool msdil1_wanted(const egne_conv_desc& d);      // msblock_dil1_f16.hip: plain f16 operands, ring-of-rows form
-int msdil1_launch(const egne_conv_desc& d, const void* fhi, float a_scale, float w_scale, const float* score_w, const float* score_c,
-                  float* s0, float* s1, int accumulate, hipStream_t st);
-
-bool msdil3_wanted(const egne_conv_desc& d);      // msblock_dil3_f16.hip: three products, ring of phase-plane rows
-int msdil3_launch(const egne_conv_desc& d, const void* fhi, const void* flo, float a_scale, float w_scale, const float* score_w,
-                  const float* score_c, float* s0, float* s1, int accumulate, hipStream_t st);
 
 inline int cdiv(long long a, long long b) { return (int)((a + b - 1) / b); }
 

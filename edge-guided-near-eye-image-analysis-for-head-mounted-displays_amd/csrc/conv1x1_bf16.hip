@@ -12,19 +12,12 @@
 // through LDS once (fp32) and leaves as 16-byte vectors of 8 channels with the lanes of a pixel side by side: whole 128-byte lines
 // per pixel for 64 output channels, residual read the same way.
 #include "common.h"
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+#include "kernel_util.h"
 
 namespace {
 
-constexpr unsigned OOB = 0x80000000u;
 constexpr int KC = 4;              // k-steps (of 32 channels) requested together: 2 x 4 loads of 16 bytes per lane in flight
 constexpr int MAXKS = 48;          // k-steps of a launch (table in the kernel arguments)
-
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const void* base, unsigned bytes) {
-  return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), 0, (int)bytes, 0x00020000);
-}
 
 // per k-step: slice index and first channel of the step inside the slice
 struct KTab { unsigned char seg[MAXKS]; unsigned short c0[MAXKS]; };

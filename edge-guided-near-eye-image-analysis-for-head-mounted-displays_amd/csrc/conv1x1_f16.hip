@@ -15,22 +15,10 @@
 // pack (egne_pack_conv1x1_weight_f16) uses the same order.  The product is computed transposed (weights as the
 // A operand): a lane ends up with 4 consecutive output channels of one pixel -> 16-byte stores.
 #include "common.h"
+#include "kernel_util.h"
 #include "split_f16.h"
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef _Float16 h8 __attribute__((ext_vector_type(8)));
-typedef _Float16 h2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-
 namespace {
-
-constexpr unsigned OOB = 0x80000000u;
-
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const void* base, unsigned bytes) {
-  return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), 0, (int)bytes, 0x00020000);
-}
 
 __device__ __forceinline__ void split8(const u32x4 a, const u32x4 b, float s, h8& hi, h8& lo) {
   const f32x4 va = __builtin_bit_cast(f32x4, a), vb = __builtin_bit_cast(f32x4, b);
@@ -442,11 +430,8 @@ extern "C" int egne_conv1x1_f16x3_fwd(const egne_conv_desc* dp, const void* fhi,
   const int TN = d.CoutP == 32 ? 1 : 2;
   const size_t lds = (size_t)G * TN * 2 * 64 * 8 * sizeof(_Float16);
   EGNE_REQUIRE(lds <= 80 * 1024, "conv1x1_f16: K = %d groups of 16 does not fit the LDS weight image", G);
-  static bool once = [] {
-    return hipFuncSetAttribute((const void*)conv1x1_f16x3_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024) == hipSuccess &&
-           hipFuncSetAttribute((const void*)conv1x1_f16x3_kernel<2>, hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024) == hipSuccess;
-  }();
-  if (!once) return egne::fail(EGNE_ERR_LAUNCH, "conv1x1_f16: cannot raise the dynamic LDS limit");
+  if (!egne::raise_lds_all(80 * 1024, conv1x1_f16x3_kernel<1>, conv1x1_f16x3_kernel<2>))
+    return egne::fail(EGNE_ERR_LAUNCH, "conv1x1_f16: cannot raise the dynamic LDS limit");
   const int ny = d.CoutP / (32 * TN);
   long long gx = (nb + 3) / 4;
   const long long cap = 256 * 8;
@@ -456,11 +441,8 @@ extern "C" int egne_conv1x1_f16x3_fwd(const egne_conv_desc* dp, const void* fhi,
   if (up) {
     const size_t lds_up = lds + (size_t)4 * 18 * (32 * TN + 8) * sizeof(float);       // + a patch of the addend per wave
     EGNE_REQUIRE(lds_up <= 80 * 1024, "conv1x1_f16: K = %d groups of 16 leaves no room for the addend patches", G);
-    static bool once_up = [] {
-      return hipFuncSetAttribute((const void*)conv1x1_f16x3_kernel<1, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024) == hipSuccess &&
-             hipFuncSetAttribute((const void*)conv1x1_f16x3_kernel<2, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024) == hipSuccess;
-    }();
-    if (!once_up) return egne::fail(EGNE_ERR_LAUNCH, "conv1x1_f16: cannot raise the dynamic LDS limit");
+    if (!egne::raise_lds_all(80 * 1024, conv1x1_f16x3_kernel<1, true>, conv1x1_f16x3_kernel<2, true>))
+      return egne::fail(EGNE_ERR_LAUNCH, "conv1x1_f16: cannot raise the dynamic LDS limit");
     if (TN == 1)
       hipLaunchKernelGGL((conv1x1_f16x3_kernel<1, true>), dim3((unsigned)gx, ny), dim3(256), lds_up, st, d, (const _Float16*)fhi, (const _Float16*)flo,
                          a_scale, os, G, M, (int)nb);
@@ -512,15 +494,9 @@ extern "C" int egne_conv1x1_pool2_f16x3_fwd(const egne_conv_desc* dp, const void
                "conv1x1_pool2_f16: stats_ws needs 1 <= stats_nchunk <= %d blocks per frame, no empty chunk", bpf);
   const size_t lds = (size_t)G * TN * 2 * 64 * 8 * sizeof(_Float16) + (d.stats_ws ? (size_t)4 * 32 * 36 * sizeof(float) : 0);
   EGNE_REQUIRE(lds <= 80 * 1024, "conv1x1_pool2_f16: K = %d groups of 16 does not fit the LDS weight image", G);
-  static bool once = [] {
-    return hipFuncSetAttribute((const void*)conv1x1_pool_f16x3_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024) == hipSuccess &&
-           hipFuncSetAttribute((const void*)conv1x1_pool_f16x3_kernel<2>, hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024) == hipSuccess &&
-           hipFuncSetAttribute((const void*)conv1x1_pool_f16x3_kernel<3>, hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024) == hipSuccess &&
-           hipFuncSetAttribute((const void*)conv1x1_pool_f16x3_kernel<1, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024) == hipSuccess &&
-           hipFuncSetAttribute((const void*)conv1x1_pool_f16x3_kernel<2, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024) == hipSuccess &&
-           hipFuncSetAttribute((const void*)conv1x1_pool_f16x3_kernel<3, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024) == hipSuccess;
-  }();
-  if (!once) return egne::fail(EGNE_ERR_LAUNCH, "conv1x1_pool2_f16: cannot raise the dynamic LDS limit");
+  if (!egne::raise_lds_all(80 * 1024, conv1x1_pool_f16x3_kernel<1>, conv1x1_pool_f16x3_kernel<2>, conv1x1_pool_f16x3_kernel<3>,
+                           conv1x1_pool_f16x3_kernel<1, true>, conv1x1_pool_f16x3_kernel<2, true>, conv1x1_pool_f16x3_kernel<3, true>))
+    return egne::fail(EGNE_ERR_LAUNCH, "conv1x1_pool2_f16: cannot raise the dynamic LDS limit");
   const int ny = 1;
   const long long nu = d.stats_ws ? (long long)d.B * d.stats_nchunk : nb;       // units of work: one per wave and turn (see the kernel)
   long long gx = (nu + 3) / 4;

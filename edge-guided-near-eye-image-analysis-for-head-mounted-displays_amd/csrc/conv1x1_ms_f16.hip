@@ -8,24 +8,12 @@
 // pre-split f16 weights [CoutP][Ktot] staged through LDS, 128x128 or 256x64 tiles, two barriers per 32-channel step --
 // the structure of conv_f16x3_kernel without taps, padding masks or groups.
 #include "common.h"
+#include "kernel_util.h"
 #include "split_f16.h"
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef _Float16 h8 __attribute__((ext_vector_type(8)));
-typedef _Float16 h4 __attribute__((ext_vector_type(4)));
-typedef _Float16 h2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
 namespace {
 
-constexpr unsigned OOB = 0x80000000u;
 constexpr int KC = 32, LDH = 40;
-
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const void* base, unsigned bytes) {
-  return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), 0, (int)bytes, 0x00020000);
-}
 
 template <int WGM, int WGN, int TM, int TN>
 __global__ __launch_bounds__(256) void conv1x1_ms_f16x3_kernel(const egne_conv_desc p, const _Float16* __restrict__ whi,

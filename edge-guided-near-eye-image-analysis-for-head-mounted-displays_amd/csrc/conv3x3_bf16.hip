@@ -17,12 +17,10 @@
 //             MFMAs of tap t; transposed product, so a lane ends with 4 consecutive channels of a pixel per accumulator:
 //             8-byte stores, issued between the MFMAs of the next tile's first job.
 #include "common.h"
+#include "kernel_util.h"
 #include <cstdlib>
 #include <type_traits>
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
 typedef egne_bf16x8 b8;
 
 #ifdef EGNE_B3_STAMPS      // diagnostic build only (scratch/b3_stamps.py): cycles per phase and wave, [block][wave][4]
@@ -45,17 +43,6 @@ constexpr int TW = 32, TH = 8, HWd = TW + 2, HHd = TH + 2, NPX = HHd * HWd;     
 constexpr int IMG = NPX * 32;                            // bf16 elements per image
 constexpr int WCH = 9 * 2 * 512;                         // bf16 elements of weights per 32-channel chunk
 constexpr int NI = (NPX * 4 + 255) / 256;                // 16-byte items per producer lane and job (6)
-constexpr unsigned OOB = 0x80000000u;
-
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const void* base, unsigned bytes) {
-  return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), 0, (int)bytes, 0x00020000);
-}
-
-__device__ __forceinline__ void lds_barrier() {
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  __builtin_amdgcn_s_barrier();
-  asm volatile("" ::: "memory");
-}
 
 // Output-channel order of a 32-channel block inside the LDS weight images (round 6).  The consumer's two fragments nh = 0 / 1 of a block
 // are the LDS lane positions 16 nh + i (i = MFMA row), and the transposed product leaves rows 4 kg .. 4 kg + 3 of a fragment in lane

@@ -22,32 +22,14 @@
 // the same FLOP per cycle (MI355X DVFS give-back, shape effect); pixel pitch 48 halfs keeps its ds_read_b128 pattern
 // conflict-free (40 for the 32x32x16 pattern).
 #include "common.h"
+#include "kernel_util.h"
 #include "split_f16.h"
 #include <type_traits>
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef _Float16 h8 __attribute__((ext_vector_type(8)));
-typedef _Float16 h4 __attribute__((ext_vector_type(4)));
-typedef _Float16 h2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
 namespace {
 __device__ int g_rs_prio = 0;
 
 constexpr int TW = 32, HWd = TW + 2;
-constexpr unsigned OOB = 0x80000000u;
-
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const void* base, unsigned bytes) {
-  return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), 0, (int)bytes, 0x00020000);
-}
-
-__device__ __forceinline__ void lds_barrier() {
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  __builtin_amdgcn_s_barrier();
-  asm volatile("" ::: "memory");
-}
 
 // NCH: 32-channel chunks of the input slice (1 or 2); WN: 32-wide output tiles (1, 2 or 4); TH: tile rows (8 with one chunk,
 // 4 with two: what two LDS images leave room for).  Consumer wave -> (rows, output tiles): NSPLIT waves share a row group.
@@ -584,8 +566,7 @@ int launch_rs(const egne_conv_desc& d, const _Float16* fhi, const _Float16* flo,
   const int tiles_x = (d.W + TW - 1) / TW, tiles_y = (d.H + TH - 1) / TH;
   const int ntiles = tiles_x * tiles_y * d.B;
   constexpr size_t lds = RsGeom<NCH, TH, M16>::LDS_BYTES;
-  static bool once = hipFuncSetAttribute((const void*)conv3x3_rs_kernel<NCH, WN, TH, M16, DBG, TPO>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) == hipSuccess;
-  if (!once) return egne::fail(EGNE_ERR_LAUNCH, "conv3x3_rs: cannot raise the dynamic LDS limit to %zu", lds);
+  if (!egne::raise_lds((const void*)conv3x3_rs_kernel<NCH, WN, TH, M16, DBG, TPO>, lds)) return egne::fail(EGNE_ERR_LAUNCH, "conv3x3_rs: cannot raise the dynamic LDS limit to %zu", lds);
   int gx = 256;
   if (gx > ntiles) gx = ntiles;
   hipLaunchKernelGGL((conv3x3_rs_kernel<NCH, WN, TH, M16, DBG, TPO>), dim3(gx), dim3(512), lds, st, d, fhi, flo, a_scale, os, tiles_x, tiles_y, ntiles);

@@ -32,16 +32,10 @@
 // (sched_group_barrier; the ISA of a tap is M d v v v M d v v v ...).  Three products, 64 -> 64 at 240x320x64: 1.23 -> 1.03 ms, a
 // consumer's work per job 7 000 -> 4 610 cycles against 3 456 of MFMA issue -- and level with the producers' 4 700, which now co-limit.
 #include "common.h"
+#include "kernel_util.h"
 #include "split_f16.h"
 #include <cstdlib>
 #include <type_traits>
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 h8 __attribute__((ext_vector_type(8)));
-typedef _Float16 h4 __attribute__((ext_vector_type(4)));
-typedef _Float16 h2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
 
 namespace {
 __device__ int g_wdbg = 0;
@@ -51,17 +45,6 @@ constexpr int TW = 32, TH = 8, HWd = TW + 2, HHd = TH + 2, NPX = HHd * HWd;     
 constexpr int IMGH = 2 * NPX * 32;                       // halfs per image: [hi | lo][NPX][32]
 constexpr int WCH = 9 * 2 * 2 * 512;                     // halfs of weights per 32-channel chunk
 constexpr int NI = (NPX * 8 + 255) / 256;                // 16-byte items per producer lane and job
-constexpr unsigned OOB = 0x80000000u;
-
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const void* base, unsigned bytes) {
-  return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), 0, (int)bytes, 0x00020000);
-}
-
-__device__ __forceinline__ void lds_barrier() {
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  __builtin_amdgcn_s_barrier();
-  asm volatile("" ::: "memory");
-}
 
 // KCH: 32-channel chunks of the input slice (1 or 2: all weights resident) or 0: any number of chunks (p.Ktot / 32), the weights of
 // a job's chunk (36 KB) STREAMED into one of two LDS weight buffers by the producers one job ahead -- the wider layers
@@ -805,8 +788,7 @@ int launch_rw_form(const egne_conv_desc& d, const _Float16* fhi, const _Float16*
   const int ntiles = tiles_x * tiles_y * d.B, ncb = d.CoutP / 32, nrun = (d.Cout_store + 31) / 32;
   constexpr size_t lds = ((size_t)2 * IMGH + (size_t)(KCH == 0 ? 2 : KCH) * WCH) * sizeof(_Float16);
   static_assert(lds <= 163840, "LDS budget");
-  static bool once = hipFuncSetAttribute((const void*)conv3x3_rw_kernel<KCH, NP, F16IN, SH>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) == hipSuccess;
-  if (!once) return egne::fail(EGNE_ERR_LAUNCH, "conv3x3_rw: cannot raise the dynamic LDS limit to %zu", lds);
+  if (!egne::raise_lds((const void*)conv3x3_rw_kernel<KCH, NP, F16IN, SH>, lds)) return egne::fail(EGNE_ERR_LAUNCH, "conv3x3_rw: cannot raise the dynamic LDS limit to %zu", lds);
   // 256 workgroups = 8 XCDs x 32; the ncb blocks of a worker sit on one XCD: 32 / ncb workers per XCD
   hipLaunchKernelGGL((conv3x3_rw_kernel<KCH, NP, F16IN, SH>), dim3(256), dim3(512), lds, st, d, fhi, flo, a_scale, os, tiles_x, tiles_y, ntiles, ncb, nrun);
   return egne::check_launch("egne_conv3x3_rw_f16_fwd");

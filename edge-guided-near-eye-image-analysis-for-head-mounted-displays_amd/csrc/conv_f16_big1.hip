@@ -15,25 +15,12 @@
 //   * the 16-byte chunk c of row r sits at chunk c ^ g((r >> 2) & 3), g = (0, 2, 3, 1): conflict free for the lane groups of
 //     ds_read_b128 in the 16 x 16 x 32 operand pattern (16 rows x 4 chunks) and for the ds_write_b64 of the conversion.
 #include "common.h"
+#include "kernel_util.h"
 #include <type_traits>
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef _Float16 h8 __attribute__((ext_vector_type(8)));
-typedef _Float16 h4 __attribute__((ext_vector_type(4)));
-typedef _Float16 h2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-typedef __attribute__((address_space(3))) void* lds_ptr;
 
 namespace {
 
-constexpr unsigned OOB = 0x80000000u;
 constexpr int BM = 256, ROWB = 64, NSTG = 4;
-
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const void* base, unsigned bytes) {
-  return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), 0, (int)bytes, 0x00020000);
-}
 
 // chunk swizzle key of row r
 __host__ __device__ __forceinline__ constexpr int swz(int r) {

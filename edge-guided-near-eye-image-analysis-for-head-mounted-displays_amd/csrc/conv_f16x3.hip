@@ -12,13 +12,9 @@
 // float64 convolution 4e-7..2e-6 (the fp32 CPU convolution: 2e-7..3e-7), edge map within 3e-6 of the reference;
 // ESF-Net (training, gradients) stays on the exact-fp32 kernels.
 #include "common.h"
+#include "kernel_util.h"
 #include "split_f16.h"
 #include <cstdlib>
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 h8 __attribute__((ext_vector_type(8)));
-typedef _Float16 h4 __attribute__((ext_vector_type(4)));
 
 namespace {
 
@@ -29,15 +25,6 @@ __device__ __forceinline__ float act_apply(float v, int act) {
   if (act == EGNE_ACT_RELU) return fmaxf(v, 0.f);
   if (act == EGNE_ACT_LEAKY) return v > 0.f ? v : 0.01f * v;
   return v;
-}
-
-typedef _Float16 h2 __attribute__((ext_vector_type(2)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-constexpr unsigned OOB = 0x80000000u;
-
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const void* base, unsigned bytes) {
-  return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), 0, (int)bytes, 0x00020000);
 }
 
 // 4 waves arranged WGM x WGN, each wave owns TM x TN MFMA tiles (32x32).  Shapes instantiated:

@@ -24,28 +24,14 @@
 // (taps outside the image and rows past the batch through the out-of-range offset: zeros), no registers, no VALU, no ds_write.  The operands,
 // the K order and the order of the three products are those of the converting path: the results agree bit for bit.
 #include "common.h"
+#include "kernel_util.h"
 #include "split_f16.h"
 #include <cstdlib>
 #include <type_traits>
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef _Float16 h8 __attribute__((ext_vector_type(8)));
-typedef _Float16 h4 __attribute__((ext_vector_type(4)));
-typedef _Float16 h2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-typedef __attribute__((address_space(3))) void* lds_ptr;
-
 namespace {
 
-constexpr unsigned OOB = 0x80000000u;
 constexpr int BM = 256, ROWB = 128;
-
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const void* base, unsigned bytes) {
-  return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), 0, (int)bytes, 0x00020000);
-}
 
 // NB = 32-channel blocks per wave along N (2 -> BN = 256 with 4 waves along N, 1 -> BN = 128)
 // NP = products per multiply: 3 (hi hi + hi lo + lo hi) or 1 (hi hi: plain f16 operands; egne_conv_desc.f16_products) -- the lo halves
@@ -417,18 +403,14 @@ extern "C" int egne_conv2d_f16x3_big_fwd(const egne_conv_desc* dp, const void* w
 #undef EGNE_BIGP_GO
     return egne::check_launch("egne_conv2d_f16x3_big_fwd");
   }
-  static bool once = [] {
-    return hipFuncSetAttribute((const void*)conv_f16x3_big_kernel<2, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024) == hipSuccess &&
-           hipFuncSetAttribute((const void*)conv_f16x3_big_kernel<1, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024) == hipSuccess &&
-           hipFuncSetAttribute((const void*)conv_f16x3_big_kernel<2, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024) == hipSuccess &&
-           hipFuncSetAttribute((const void*)conv_f16x3_big_kernel<1, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024) == hipSuccess;
-  }();
   static const bool m16 = !(getenv("EGNE_BIG_M16") && atoi(getenv("EGNE_BIG_M16")) == 0);     // MFMA shape (header)
-  if (!once) return egne::fail(EGNE_ERR_LAUNCH, "conv_f16x3_big: cannot raise the dynamic LDS limit");
+  // (the kernels are emitted in the order they are named here)
+  if (!egne::raise_lds((const void*)conv_f16x3_big_kernel<2, false>, 128 * 1024) || !egne::raise_lds((const void*)conv_f16x3_big_kernel<1, false>, 96 * 1024) ||
+      !egne::raise_lds((const void*)conv_f16x3_big_kernel<2, true>, 128 * 1024) || !egne::raise_lds((const void*)conv_f16x3_big_kernel<1, true>, 96 * 1024))
+    return egne::fail(EGNE_ERR_LAUNCH, "conv_f16x3_big: cannot raise the dynamic LDS limit");
   if (d.f16_products == 1) {       // plain f16 operands (the edge network next to a bf16-storage training plan): 16x16x32 shape only
-    static bool once1 = hipFuncSetAttribute((const void*)conv_f16x3_big_kernel<2, true, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024) == hipSuccess &&
-                        hipFuncSetAttribute((const void*)conv_f16x3_big_kernel<1, true, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024) == hipSuccess;
-    if (!once1) return egne::fail(EGNE_ERR_LAUNCH, "conv_f16x3_big: cannot raise the dynamic LDS limit");
+    if (!egne::raise_lds((const void*)conv_f16x3_big_kernel<2, true, 1>, 128 * 1024) || !egne::raise_lds((const void*)conv_f16x3_big_kernel<1, true, 1>, 96 * 1024))
+      return egne::fail(EGNE_ERR_LAUNCH, "conv_f16x3_big: cannot raise the dynamic LDS limit");
     if (d.CoutP % 256 == 0)
       hipLaunchKernelGGL((conv_f16x3_big_kernel<2, true, 1>), dim3((unsigned)((M + BM - 1) / BM), (unsigned)(d.CoutP / 256)), dim3(512), 2 * (BM + 256) * ROWB, st, d, (const char*)wimg, a_scale, os);
     else

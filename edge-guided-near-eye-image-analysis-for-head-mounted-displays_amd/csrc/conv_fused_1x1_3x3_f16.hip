@@ -19,34 +19,22 @@
 // never covers the latency of a later one, and the HBM latency of tile i+1 hides behind the matrix work of tile i.
 // Tiles are dealt so that the workgroups of one XCD work on neighbouring tiles (halo overlap served by that XCD's L2).
 #include "common.h"
+#include "kernel_util.h"
 #include "epilogue32.h"
 #include "split_f16.h"
 #include <type_traits>
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef _Float16 h8 __attribute__((ext_vector_type(8)));
-typedef _Float16 h4 __attribute__((ext_vector_type(4)));
-typedef _Float16 h2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
 namespace {
 __device__ int g_dbg = 0;
 __device__ unsigned long long g_stamps[256 * 8 * 4];
 
 constexpr int LDH = 40, TW = 32, HWd = TW + 2, MAXG = 48;
-constexpr unsigned OOB = 0x80000000u;
 
 struct GroupTab {
   int v[MAXG];       // per 16-channel group: (slice << 16) | (8-channel tail << 15) | group index inside the slice
   int off[MAXG];     // UNI: byte offset of the group's first channel inside a pixel of the common buffer
   int dn;            // UNI: groups flagged 0x4000 in v[] start dn samples further into that buffer (the edge pass' half of a 2B batch)
 };
-
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const void* base, unsigned bytes) {
-  return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), 0, (int)bytes, 0x00020000);
-}
 
 __device__ __forceinline__ void split8(const u32x4 a, const u32x4 b, float s, h8& hi, h8& lo) {
   const f32x4 va = __builtin_bit_cast(f32x4, a), vb = __builtin_bit_cast(f32x4, b);
@@ -58,12 +46,6 @@ __device__ __forceinline__ void split8(const u32x4 a, const u32x4 b, float s, h8
     hi[2 * q] = h[0]; hi[2 * q + 1] = h[1];
     lo[2 * q] = l[0]; lo[2 * q + 1] = l[1];
   }
-}
-
-__device__ __forceinline__ void lds_barrier() {
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  __builtin_amdgcn_s_barrier();
-  asm volatile("" ::: "memory");
 }
 
 // NCH: 32-channel chunks of the intermediate (1x1 output = 3x3 input); WN: 32-wide output tiles of the 3x3 (CoutP2 = 32*WN);
@@ -678,9 +660,7 @@ int launch_fused(const egne_conv_desc& d1, const egne_conv_desc& d2, const Group
   const size_t lds = (size_t)2 * 2 * NCH * (TH + 2) * HWd * LDH * sizeof(_Float16) + 32 * NCH * sizeof(float) + (NCH == 1 ? (size_t)G1 * 2048 : (size_t)(G1 < 7 ? G1 : 7) * 4096) +
                      (UPADD ? (size_t)2 * (TH / 2 + 2) * (TW / 2 + 2) * (32 * NCH + 4) * sizeof(float) : 0) +
                      (C1V ? ((size_t)2 * (TH + 4) * (TW + 4) + 32 * 12) * sizeof(float) : 0);
-  static bool once = hipFuncSetAttribute((const void*)fused_1x1_3x3_kernel<NCH, WN, TH, NB, C4, UPADD, UNI, GL, C1V>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                         160 * 1024) == hipSuccess;
-  if (!once || lds > 160 * 1024) return egne::fail(EGNE_ERR_LAUNCH, "conv_fused_1x1_3x3: %zu bytes of LDS", lds);
+  if (!egne::raise_lds((const void*)fused_1x1_3x3_kernel<NCH, WN, TH, NB, C4, UPADD, UNI, GL, C1V>, 160 * 1024) || lds > 160 * 1024) return egne::fail(EGNE_ERR_LAUNCH, "conv_fused_1x1_3x3: %zu bytes of LDS", lds);
   int gx = 256;
   if (gx > ntiles) gx = ntiles;
   hipLaunchKernelGGL((fused_1x1_3x3_kernel<NCH, WN, TH, NB, C4, UPADD, UNI, GL, C1V>), dim3(gx), dim3(512), lds, st, d1, d2, gt, w1hi, w1lo, G1, f2hi, f2lo, a1, os1,

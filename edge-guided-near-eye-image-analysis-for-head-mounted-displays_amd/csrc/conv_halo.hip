@@ -11,10 +11,8 @@
 // [tap][k/8][n/32][lane][4] so that each wave fetches its B fragment with one fully coalesced
 // 1-KiB global load (L2/L1 resident, prefetched one k-step ahead).
 #include "common.h"
+#include "kernel_util.h"
 #include <cstdlib>
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 namespace {
 
@@ -27,13 +25,6 @@ __device__ __forceinline__ float act1(float v, int act) {
   if (act == EGNE_ACT_RELU) return fmaxf(v, 0.f);
   if (act == EGNE_ACT_LEAKY) return v > 0.f ? v : 0.01f * v;
   return v;
-}
-
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-constexpr unsigned OOB = 0x80000000u;
-
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const void* base, unsigned bytes) {
-  return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), 0, (int)bytes, 0x00020000);
 }
 
 // All global traffic goes through BUFFER instructions on per-frame resources (see conv_halo_f16.hip): tile-independent

@@ -15,10 +15,8 @@
 // LDS = 49 KB halo + 36*WN KB weights  ->  one 256-thread workgroup per CU (1 wave per SIMD), which is
 // what the register budget of the deferred epilogue wants anyway.
 #include "common.h"
+#include "kernel_util.h"
 #include <cstdlib>
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 namespace {
 
@@ -280,11 +278,8 @@ int launch3(const egne_conv_desc& d, hipStream_t st) {
   int gx = (256 + ny - 1) / ny;      // one workgroup per CU in total
   if (gx > ntiles) gx = ntiles;
   if (gx < 1) gx = 1;
-  static bool attr_set = false;
-  if (!attr_set) {
-    hipFuncSetAttribute((const void*)conv3x3_halo3_kernel<WM, WN, D>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    attr_set = true;
-  }
+  if (!egne::raise_lds((const void*)conv3x3_halo3_kernel<WM, WN, D>, 160 * 1024))
+    return egne::fail(EGNE_ERR_LAUNCH, "conv3x3_halo (v3): cannot raise the dynamic LDS limit");
   hipLaunchKernelGGL((conv3x3_halo3_kernel<WM, WN, D>), dim3(gx, ny), dim3(256), lds, st, d, d.w, tiles_x, tiles_y, ntiles);
   return egne::check_launch("egne_conv3x3_halo_fwd(v3)");
 }

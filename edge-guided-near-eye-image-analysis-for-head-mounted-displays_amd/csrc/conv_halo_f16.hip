@@ -8,12 +8,8 @@
 // are address offsets into it.  Weight fragments ([tap][k/16][n/32][lane][8 halfs], hi and lo) come from L2
 // through a 4-slot register ring; workgroups walk tiles grid-stride with the next halo prefetched.
 #include "common.h"
+#include "kernel_util.h"
 #include "split_f16.h"
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 h8 __attribute__((ext_vector_type(8)));
-typedef _Float16 h4 __attribute__((ext_vector_type(4)));
 
 namespace {
 
@@ -36,14 +32,6 @@ __device__ __forceinline__ float act1(float v, int act) {
 // weight ring, the residual and the output use 32-bit byte offsets that are tile-independent per lane plus one
 // scalar per tile, and out-of-image / padded lanes carry the offset 0x80000000, which the range check of the
 // buffer unit turns into a zero load or a dropped store -- no per-lane 64-bit address math and no selects.
-typedef _Float16 h2 __attribute__((ext_vector_type(2)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-constexpr unsigned OOB = 0x80000000u;
-
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const void* base, unsigned bytes) {
-  return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), 0, (int)bytes, 0x00020000);
-}
 
 // NW = waves along N: <WM=2, WN, NW=1> gives every wave 2 tile rows x all 32*WN channels; <WM=4, WN=1, NW=2> gives a
 // wave 4 tile rows x 32 of the 64 channels -- same accumulators, but each weight fragment fetched from L1/L2 feeds

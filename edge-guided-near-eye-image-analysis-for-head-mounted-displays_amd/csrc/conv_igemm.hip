@@ -15,10 +15,8 @@
 // `ngroups`=3 runs the three dilated 3x3 convs of a BDCN MSBlock back to back on one accumulator
 // set and sums relu(conv_g) in registers; the block's first conv output is added as `residual`.
 #include "common.h"
+#include "kernel_util.h"
 #include <cstdlib>
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 namespace {
 
@@ -34,10 +32,6 @@ __device__ __forceinline__ float act_apply(float v, int act) {
   if (act == EGNE_ACT_LEAKY) return v > 0.f ? v : 0.01f * v;
   return v;
 }
-
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-constexpr unsigned OOB = 0x80000000u;
 
 // Four consecutive channels of an activation tensor through a buffer resource: 16 bytes of fp32 or 8 bytes of bf16
 // (egne_conv_desc.dtype); `off` is a BYTE offset.  Raw<TS> is what stays in registers until the values are needed.
@@ -63,10 +57,6 @@ template <typename TS> __device__ __forceinline__ void store_el(float v, __amdgp
 template <typename TS> __device__ __forceinline__ void store_4(f32x4 v, __amdgpu_buffer_rsrc_t r, int off) {
   if constexpr (sizeof(TS) == 4) __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), r, off, 0, 0);
   else __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2, __builtin_convertvector(v, egne_bf16x4)), r, off, 0, 0);
-}
-
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const void* base, unsigned bytes) {
-  return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), 0, (int)bytes, 0x00020000);
 }
 
 // Addressing: a staged row keeps ONE pixel index relative to the first frame of the tile (slice independent) and a

@@ -11,19 +11,11 @@
 // product is transposed (weights as the 16-row A operand, rows 8-15 zero) so that a lane ends with 4 consecutive output channels of
 // one pixel.  Eight waves, one output row each; the next tile's halo is requested before the current tile's MFMAs.
 #include "common.h"
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
+#include "kernel_util.h"
 
 namespace {
 
 constexpr int TW = 32, TH = 8, NT = 512;
-constexpr unsigned OOB = 0x80000000u;
-
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const void* base, unsigned bytes) {
-  return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), 0, (int)bytes, 0x00020000);
-}
 
 // K: kernel size (kh = kw = K), NCH: 32-channel chunks of the input slice
 template <int K, int NCH>
@@ -136,8 +128,7 @@ int launch_narrow(const egne_conv_desc& d, hipStream_t st) {
   const int ntiles = tiles_x * tiles_y * d.B;
   constexpr size_t lds = ((size_t)(TH + K - 1) * (TW + K - 1) * (NCH * 32 + 8) + (size_t)K * K * NCH * 8 * 32) * sizeof(egne_bf16);
   static_assert(lds <= 163840, "LDS budget");
-  static bool once = hipFuncSetAttribute((const void*)conv_narrow_bf16_kernel<K, NCH>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) == hipSuccess;
-  if (!once) return egne::fail(EGNE_ERR_LAUNCH, "conv_narrow_bf16: cannot raise the dynamic LDS limit to %zu", lds);
+  if (!egne::raise_lds((const void*)conv_narrow_bf16_kernel<K, NCH>, lds)) return egne::fail(EGNE_ERR_LAUNCH, "conv_narrow_bf16: cannot raise the dynamic LDS limit to %zu", lds);
   hipLaunchKernelGGL((conv_narrow_bf16_kernel<K, NCH>), dim3(ntiles < 256 ? ntiles : 256), dim3(NT), lds, st, d, tiles_x, tiles_y, ntiles);
   return egne::check_launch("egne_conv_narrow_bf16_fwd");
 }

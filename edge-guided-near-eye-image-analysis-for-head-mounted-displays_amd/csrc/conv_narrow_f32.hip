@@ -10,9 +10,8 @@
 // v_fmac directly -- no LDS reads, no vector registers.  One rounding per operation, fp32 accumulation in a fixed order (tap-major,
 // then channel): closer to the reference's fp32 convolution than the split-f16 products of the other layers.
 #include "common.h"
+#include "kernel_util.h"
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 // the weight pack read through the CONSTANT address space: uniform addresses then load through the scalar cache (s_load_dwordx16)
 // and the values feed v_fmac as scalar operands.  (Through a plain global pointer hipcc issued a vector global_load_dwordx4 and a
 // full vmcnt(0) wait per four multiply-adds: the pack might alias the output.)  Nothing in a launch writes the pack.
@@ -21,11 +20,6 @@ typedef __attribute__((address_space(4))) const float cfloat;
 namespace {
 
 constexpr int TW = 32, TH = 8, HWd = TW + 2, HHd = TH + 2, NPX = HHd * HWd, NT = 256;
-constexpr unsigned OOB = 0x80000000u;
-
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const void* base, unsigned bytes) {
-  return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), 0, (int)bytes, 0x00020000);
-}
 
 // NCH: 32-channel chunks of the input slice.  p.w = [9 taps][32 NCH channels][4 outputs] fp32 (egne_pack_conv3x3_narrow_weight): the
 // four outputs of a (tap, channel) are neighbours, so a 64-bit scalar pair is the operand of one packed multiply-add (from the
@@ -206,8 +200,7 @@ extern "C" int egne_conv3x3_narrow_fwd(const egne_conv_desc* dp, void* stream) {
   int gx = 256 * (nch == 1 ? 3 : 1);                  // 48 KB of LDS per workgroup with 32 channels: three per CU
   if (gx > ntiles) gx = ntiles;
   hipStream_t st = (hipStream_t)stream;
-  static bool once = hipFuncSetAttribute((const void*)conv3x3_narrow_f32_kernel<2>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024) == hipSuccess;
-  if (!once) return egne::fail(EGNE_ERR_LAUNCH, "conv3x3_narrow: %zu bytes of LDS", lds);
+  if (!egne::raise_lds((const void*)conv3x3_narrow_f32_kernel<2>, 96 * 1024)) return egne::fail(EGNE_ERR_LAUNCH, "conv3x3_narrow: %zu bytes of LDS", lds);
   if (nch == 1) hipLaunchKernelGGL(conv3x3_narrow_f32_kernel<1>, dim3(gx), dim3(NT), lds, st, d, tiles_x, tiles_y, ntiles);
   else hipLaunchKernelGGL(conv3x3_narrow_f32_kernel<2>, dim3(gx), dim3(NT), lds, st, d, tiles_x, tiles_y, ntiles);
   return egne::check_launch("egne_conv3x3_narrow_fwd");

@@ -227,8 +227,7 @@ extern "C" int egne_spatial_weights(const int64_t* label, int B, int H, int W, f
   EGNE_REQUIRE(label && out && B > 0 && H > 1 && W > 1, "spatial_weights: bad arguments");
   const size_t lds = (size_t)2 * H * W;
   EGNE_REQUIRE(lds <= 156 * 1024, "spatial_weights: a %dx%d map does not fit the LDS (2 bytes per pixel, 156 KB)", H, W);
-  static bool once = hipFuncSetAttribute((const void*)spatial_weights_k, hipFuncAttributeMaxDynamicSharedMemorySize, 156 * 1024) == hipSuccess;
-  if (!once) return egne::fail(EGNE_ERR_LAUNCH, "spatial_weights: cannot raise the dynamic LDS limit");
+  if (!egne::raise_lds((const void*)spatial_weights_k, 156 * 1024)) return egne::fail(EGNE_ERR_LAUNCH, "spatial_weights: cannot raise the dynamic LDS limit");
   hipLaunchKernelGGL(spatial_weights_k, dim3(B), dim3(1024), lds, (hipStream_t)stream, (const long long*)label, H, W, out);
   return egne::check_launch("egne_spatial_weights");
 }

@@ -2,8 +2,7 @@
 // upsampling, layout conversion, small activations.  All loads/stores are 16 B per lane along the
 // channel axis (slices are 16-B aligned and padded to multiples of 8 channels).
 #include "common.h"
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
+#include "kernel_util.h"
 
 namespace {
 

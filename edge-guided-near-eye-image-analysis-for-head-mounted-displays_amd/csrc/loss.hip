@@ -7,8 +7,7 @@
 // class-presence test replaces np.unique(target.cpu()) of loss.py:98,127) and reduces over the batch.
 // Both passes are deterministic (no atomics).
 #include "common.h"
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
+#include "kernel_util.h"
 
 namespace {
 

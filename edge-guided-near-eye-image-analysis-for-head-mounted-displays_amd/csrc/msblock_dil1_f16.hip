@@ -2,7 +2,7 @@
 // training plan with bf16 activation storage), input in split-pair storage (only its hi plane is read):
 //   out = o + sum_g relu(conv3x3_{dil g}(o) + b_g), g = 0..2, dilations 4 / 8 / 12 (bdcn_new.py:51-54), score heads fused,
 // one v_mfma_f32_16x16x32_f16 per product, fp32 accumulate; the same operands and per-accumulator order as msblock_dil_ps_f16.hip
-// with NP = 1, so the two agree bit for bit.
+// with NP = 1 and the epilogue both take from msblock_dil_common.h, so the two agree bit for bit.
 //
 // Why a kernel of its own.  msblock_dil_ps_f16.hip stages, per 8 x 32 tile, nine strips (one per dilation and kernel row) through two
 // LDS buffers: 13.7x the tile's own bytes from L2 and a barrier every 12 MFMAs per wave once the three-product split is gone
@@ -17,14 +17,11 @@
 //   * 16-byte chunk c of ring pixel q sits at c ^ (2 * ((q >> 2) & 1)): conflict free for the 16-pixel x 4-chunk ds_read_b128
 //     pattern at every column offset that is a multiple of four (all tap offsets are).
 #include "common.h"
+#include "kernel_util.h"
+#include "msblock_dil_common.h"
 #include <cstdlib>
 #include <type_traits>
 #include <utility>
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 h8 __attribute__((ext_vector_type(8)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(3))) void* lds_ptr;
 
 namespace {
 
@@ -35,18 +32,7 @@ constexpr int WLDS = 2 * 9 * 2 * 1024;                                // dilatio
 constexpr int OFF_W = RINGB, OFF_DUMMY = OFF_W + WLDS, OFF_CONST = OFF_DUMMY + 1024;
 constexpr int LDS_BYTES = OFF_CONST + 164 * 4;
 constexpr int GI = RPX * TH / 16;                                     // 28 LDS-DMA instructions per 8-row group
-constexpr unsigned OOB = 0x80000000u;
 static_assert(LDS_BYTES <= 163840, "LDS budget");
-
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const void* base, unsigned bytes) {
-  return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), 0, (int)bytes, 0x00020000);
-}
-
-__device__ __forceinline__ void lds_barrier() {
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  __builtin_amdgcn_s_barrier();
-  asm volatile("" ::: "memory");
-}
 
 struct Tap { int g, ky, kx; };
 // a step's taps: the two tap rows that read the ring rows the step's DMA replaces go first (dilation 12 / kernel row 0: frame rows
@@ -76,12 +62,7 @@ void msdil1_kernel(const egne_conv_desc p, const _Float16* __restrict__ fhi, flo
   const int H = p.H, W = p.W;
   const egne_seg sg = p.seg[0];
 
-  if (tid < 160) {
-    const int r = tid >> 5, c = tid & 31;
-    lconst[tid] = r < 3 ? (p.bias ? p.bias[r * p.CoutP + c] : 0.f) : (score_w ? score_w[(r - 3) * 32 + c] : 0.f);
-  } else if (tid < 162) {
-    lconst[tid] = score_c ? score_c[tid - 160] : 0.f;
-  }
+  msdil_fill_lconst(lconst, tid, p, score_w, score_c);
   // weights: dilations 4 and 8 -> LDS (36 blocks of 1 KB, linear), dilation 12 -> registers (the A operand of tap t, channel block nh)
   const __amdgpu_buffer_rsrc_t rwh = make_rsrc(fhi, 3u * 9u * 2u * 1024u);
   for (int k = wave; k < 36; k += 8)
@@ -198,9 +179,8 @@ void msdil1_kernel(const egne_conv_desc p, const _Float16* __restrict__ fhi, flo
             lds_barrier();
             issue_group(y0 + TH + HALO, y0 & 31, t + 1 < nst);
             // the running score sums of this tile (lane (l15, kg) finishes head kg >> 1 of pixel block kg & 1); unconditional load
-            const int h = kg >> 1, y = y0 + wave, x = x0 + (kg & 1) * 16 + l15;
-            sdst = (score_w && y < H && x < W) ? (h ? s1 : s0) + ((long long)b * H + y) * W + x : nullptr;
-            sprev = *(sdst ? (const volatile float*)sdst : (const volatile float*)p.residual);
+            const int y = y0 + wave, x = x0 + (kg & 1) * 16 + l15;
+            msdil_score_prefetch(p, score_w, s0, s1, kg, b, y, x, y < H && x < W, sdst, sprev);
           }
         }()), ...);
       }(std::make_integer_sequence<int, 27>{});
@@ -210,57 +190,16 @@ void msdil1_kernel(const egne_conv_desc p, const _Float16* __restrict__ fhi, flo
       {
         const int y = y0 + wave;
         const __amdgpu_buffer_rsrc_t rout = make_rsrc(p.out ? p.out + (long long)b * H * W * p.out_pix_stride : nullptr, p.out ? frame_out : 0u);
-        f32x4 bq[3][2], cwq[2][2];
-#pragma unroll
-        for (int nh = 0; nh < 2; ++nh) {
-          const int n = nh * 16 + 4 * kg;
-#pragma unroll
-          for (int g = 0; g < 3; ++g) bq[g][nh] = *(const f32x4*)&lconst[g * 32 + n];
-#pragma unroll
-          for (int h = 0; h < 2; ++h) cwq[h][nh] = *(const f32x4*)&lconst[(3 + h) * 32 + n];
-        }
-        float sc[2][2];
+        int pix[2];
+        bool okp[2];
 #pragma unroll
         for (int ph = 0; ph < 2; ++ph) {
           const int x = x0 + ph * 16 + l15;
-          const bool okp = y < H && x < W;
-          const int pix = y * W + x;
-          sc[0][ph] = sc[1][ph] = 0.f;
-#pragma unroll
-          for (int nh = 0; nh < 2; ++nh) {
-            f32x4 v;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-              // positions 8 kg .. 8 kg + 7 of the hi plane = channels {4 kg ..} and {16 + 4 kg ..} (engine.SPLIT_PAIR_PERM); with plain
-              // f16 operands the residual is the hi half alone, as in msblock_dil_ps_f16.hip (NP = 1)
-              const float o = ((float)resh[ph][nh * 4 + e] + 0.f) * inv_a;
-              v[e] = fmaxf(acc[0][ph][nh][e] * out_scale + bq[0][nh][e], 0.f) + fmaxf(acc[1][ph][nh][e] * out_scale + bq[1][nh][e], 0.f) +
-                     fmaxf(acc[2][ph][nh][e] * out_scale + bq[2][nh][e], 0.f) + o;        // o + o1 + o2 + o3 (bdcn_new.py:54)
-              sc[0][ph] += v[e] * cwq[0][nh][e];
-              sc[1][ph] += v[e] * cwq[1][nh][e];
-              if (nh == 0 && e == 0) ovf_bad |= egne_nonfinite(acc[0][ph][nh][e] + acc[1][ph][nh][e] + acc[2][ph][nh][e] + o);
-            }
-            if (p.out) {
-              const int n = nh * 16 + 4 * kg;
-              const int oo = (okp && n < p.Cout_store) ? (pix * (int)p.out_pix_stride + p.out_ch_off + n) * 4 : (int)OOB;
-              __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), rout, oo, 0, 0);
-            }
-          }
+          okp[ph] = y < H && x < W;
+          pix[ph] = y * W + x;
         }
-        if (score_w) {
-#pragma unroll
-          for (int h = 0; h < 2; ++h)
-#pragma unroll
-            for (int ph = 0; ph < 2; ++ph) {
-              float tt = sc[h][ph];
-              tt += __shfl_xor(tt, 16);
-              tt += __shfl_xor(tt, 32);
-              sc[h][ph] = tt;
-            }
-          const int h = kg >> 1, ph = kg & 1;
-          const float v = h ? (ph ? sc[1][1] : sc[1][0]) : (ph ? sc[0][1] : sc[0][0]);
-          if (sdst) *sdst = v + (accumulate ? sprev : lconst[160 + h]);
-        }
+        // with plain f16 operands the residual is the hi half alone (LO = false), as in msblock_dil_ps_f16.hip with NP = 1
+        msdil_epilogue<2, false>(p, lconst, acc, resh, resh, pix, okp, rout, inv_a, out_scale, kg, score_w, sdst, sprev, accumulate, ovf_bad);
       }
     }
   }
@@ -277,28 +216,19 @@ bool msdil1_wanted(const egne_conv_desc& d) {
   return !(e && atoi(e) == 0) && d.f16_products == 1 && d.W >= 64 && d.H >= 48;
 }
 
-// Called by msdil_ps_launch for plain f16 operands on maps of 48 x 64 and larger; the descriptor has been validated by
-// egne_msblock_dil_scores_f16_fwd.  Work items: (frame, 32-pixel column, vertical segment); a column is cut into segments where whole
-// columns would leave compute units without work (each segment pays a 32-row warm-up).
+// Called by egne_msblock_dil_scores_f16_fwd, which has validated the descriptor, for plain f16 operands on maps of 48 x 64 and larger.
+// Work items: (frame, 32-pixel column, vertical segment); each segment pays a 32-row warm-up (3.5 steps).
 int msdil1_launch(const egne_conv_desc& d, const void* fhi, float a_scale, float w_scale, const float* score_w, const float* score_c,
                   float* s0, float* s1, int accumulate, hipStream_t st) {
+  static_assert(TH == 8, "msdil_segments counts steps of 8 rows");
   const int ncols = (d.W + TW - 1) / TW;
-  int best = 1;
-  double best_t = 1e30;
-  for (int ns = 1; ns <= 4; ++ns) {
-    const int rows = ((d.H + ns - 1) / ns + TH - 1) / TH * TH;
-    if (ns > 1 && rows * (ns - 1) >= d.H) continue;           // an empty last segment
-    const long long items = (long long)d.B * ncols * ns;
-    const double t = (double)((items + 255) / 256) * (rows / TH + 3.5);
-    if (t < best_t) { best_t = t; best = ns; }
-  }
-  const int seg_rows = ((d.H + best - 1) / best + TH - 1) / TH * TH;
-  const long long nitems = (long long)d.B * ncols * best;
+  const msdil_segs sg = msdil_segments(d.H, (long long)d.B * ncols, 3.5, 0);
+  const long long nitems = (long long)d.B * ncols * sg.nseg;
   if (!egne::raise_lds((const void*)msdil1_kernel, LDS_BYTES))
     return egne::fail(EGNE_ERR_LAUNCH, "msblock_dil (plain f16, ring form): cannot raise the dynamic LDS limit to %d", LDS_BYTES);
-  const float os = 1.0f / (a_scale * w_scale), inv_a = 1.0f / a_scale;
-  hipLaunchKernelGGL(msdil1_kernel, dim3((unsigned)(nitems < 256 ? nitems : 256)), dim3(512), LDS_BYTES, st, d, (const _Float16*)fhi, inv_a, os,
-                     ncols, best, seg_rows, (int)nitems, score_w, score_c, s0, s1, accumulate);
+  const msdil_scales sc = msdil_scales_of(a_scale, w_scale);
+  hipLaunchKernelGGL(msdil1_kernel, dim3((unsigned)(nitems < 256 ? nitems : 256)), dim3(512), LDS_BYTES, st, d, (const _Float16*)fhi, sc.inv_a, sc.os,
+                     ncols, sg.nseg, sg.seg_rows, (int)nitems, score_w, score_c, s0, s1, accumulate);
   return egne::check_launch("egne_msblock_dil_f16_fwd (plain f16, ring form)");
 }
 

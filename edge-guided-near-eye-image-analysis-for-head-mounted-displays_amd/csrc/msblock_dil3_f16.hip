@@ -1,8 +1,8 @@
 // The dilated branch of a BDCN MSBlock for an input in SPLIT-PAIR storage, three f16 products per multiply, on maps of 48 x 64 and
 // larger -- every tap read from a ring of PHASE-PLANE rows in LDS that is filled by LDS-DMA:
 //   out = o + sum_g relu(conv3x3_{dil g}(o) + b_g), g = 0..2, dilations 4 / 8 / 12 (bdcn_new.py:51-54), score heads fused.
-// Same operands, same per-accumulator order and the same epilogue expressions as msdil_ps_kernel<*, 3> (msblock_dil_ps_f16.hip): the
-// two agree bit for bit; EGNE_MSDIL3=0 (read at every launch) forces the strip kernel.
+// Same operands and per-accumulator order as msdil_ps_kernel<*, 3> (msblock_dil_ps_f16.hip), and the epilogue both take from
+// msblock_dil_common.h: the two agree bit for bit; EGNE_MSDIL3=0 (read at every launch) forces the strip kernel.
 //
 // Why.  The strip kernel stages, per 8 x 32 tile, nine strips global -> registers -> ds_write: 13.5x the tile's own bytes, every pixel
 // of o copied about 13 times; it is bound by that copy, not by its MFMAs.  The plain-f16 ring of msblock_dil1_f16.hip (32 rows x 56
@@ -21,8 +21,8 @@
 //     last two of the 40 go to a scratch KB) and 2 weight instructions per sub-step, so the counted vmcnt is uniform;
 //   * weights as in the strip kernel: the 12 fragments of (kernel row, dilation) by DMA into one of three 12 KB buffers, two
 //     sub-steps ahead, one s_barrier per sub-step (36 MFMAs of a wave).
-// Resources (hipcc -Rpass-analysis=kernel-resource-usage, gfx950): 182 VGPRs, 0 AGPRs, no VGPR spills, no scratch, 2 waves per SIMD;
-// 106 SGPRs, 67 of them parked in lanes of one VGPR (v_writelane / v_readlane) by the per-item and per-step set-up code -- none
+// Resources (make msblock_dil3_f16.s, gfx950): 183 VGPRs, 0 AGPRs, no VGPR spills, no scratch, 2 waves per SIMD;
+// 106 SGPRs, 63 of them parked in lanes of one VGPR (v_writelane / v_readlane) by the per-item and per-step set-up code -- none
 // between the barriers of a sub-step; 155 408 bytes of dynamic LDS (one workgroup of 8 waves per CU).
 //
 // What it is bound by (MI355X, 64 frames of 240 x 320, profiles/msdil3_per_layer_table.txt): 892-900 us against 1 187-1 192 us of the
@@ -32,14 +32,11 @@
 // the limit.  What is left is shared between the MFMA pipe, an item's exposed two-group warm-up, the half-empty eighth step of a
 // 60-row plane and 1.4 GB of stride-4 pixel traffic per launch; in-kernel stamps are the next step, not another guess.
 #include "common.h"
+#include "kernel_util.h"
+#include "msblock_dil_common.h"
 #include <cstdlib>
 #include <type_traits>
 #include <utility>
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 h8 __attribute__((ext_vector_type(8)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(3))) void* lds_ptr;
 
 namespace {
 
@@ -56,19 +53,8 @@ constexpr int LDS_BYTES = OFF_CONST + 164 * 4;
 constexpr int GK = GPX / 16;                                          // 19 LDS-DMA instructions per group and plane
 constexpr int GI = 2 * GK, GJ = 5;                                    // 38 per group: 5 per wave (two of the 40 into the scratch KB)
 constexpr int NS = 9;
-constexpr unsigned OOB = 0x80000000u;
 static_assert(GPX % 16 == 0 && ((GPX >> 1) & 3) == 0, "a group holds whole instructions and leaves the swizzle key alone");
 static_assert(GJ * 8 >= GI && LDS_BYTES <= 163840, "LDS budget");
-
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const void* base, unsigned bytes) {
-  return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), 0, (int)bytes, 0x00020000);
-}
-
-__device__ __forceinline__ void lds_barrier() {
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  __builtin_amdgcn_s_barrier();
-  asm volatile("" ::: "memory");
-}
 
 __global__ __launch_bounds__(512)
 void msdil3_kernel(const egne_conv_desc p, const _Float16* __restrict__ fhi, const _Float16* __restrict__ flo, float inv_a, float out_scale,
@@ -82,12 +68,7 @@ void msdil3_kernel(const egne_conv_desc p, const _Float16* __restrict__ fhi, con
   const int H = p.H, W = p.W, B = p.B;
   const egne_seg sg = p.seg[0];
 
-  if (tid < 160) {
-    const int r = tid >> 5, c = tid & 31;
-    lconst[tid] = r < 3 ? (p.bias ? p.bias[r * p.CoutP + c] : 0.f) : (score_w ? score_w[(r - 3) * 32 + c] : 0.f);
-  } else if (tid < 162) {
-    lconst[tid] = score_c ? score_c[tid - 160] : 0.f;
-  }
+  msdil_fill_lconst(lconst, tid, p, score_w, score_c);
 
   // ---- weights: the 12 fragments of sub-step S = 3 ky + g ((kx, ks) x (hi, lo), 1 KB each) into weight buffer g, two sub-steps ahead
   // of their use: wave w moves fragments w and 8 + (w & 3) (waves 4-7 repeat what waves 0-3 moved: every wave issues exactly two)
@@ -235,61 +216,18 @@ void msdil3_kernel(const egne_conv_desc p, const _Float16* __restrict__ fhi, con
           }(std::make_integer_sequence<int, 3>{});
         };
 
-        // epilogue of the step's row: lane holds channels n = 16 nh + 4 kg + e of plane pixel (y0 + wave, C0 + 16 ph + l15); the
-        // expressions of msdil_ps_kernel, in its order
+        // epilogue of the step's row: lane holds channels n = 16 nh + 4 kg + e of plane pixel (y0 + wave, C0 + 16 ph + l15)
         auto epilogue = [&] {
           const int R = y0 + wave, y = 4 * R + py;
-          f32x4 bq[3][2], cwq[2][2];
-#pragma unroll
-          for (int nh = 0; nh < 2; ++nh) {
-            const int n = nh * 16 + 4 * kg;
-#pragma unroll
-            for (int g = 0; g < 3; ++g) bq[g][nh] = *(const f32x4*)&lconst[g * 32 + n];
-#pragma unroll
-            for (int h = 0; h < 2; ++h) cwq[h][nh] = *(const f32x4*)&lconst[(3 + h) * 32 + n];
-          }
-          float sc[2][2];
-          sc[0][1] = sc[1][1] = 0.f;
+          int pix[2] = {0, 0};
+          bool okp[2] = {false, false};
 #pragma unroll
           for (int ph = 0; ph < NPH; ++ph) {
             const int Cq = C0 + ph * 16 + l15, x = 4 * Cq + px;
-            const bool okp = R < Hp && Cq < Wp;
-            const int pix = y * W + x;
-            sc[0][ph] = sc[1][ph] = 0.f;
-#pragma unroll
-            for (int nh = 0; nh < 2; ++nh) {
-              f32x4 v;
-#pragma unroll
-              for (int e = 0; e < 4; ++e) {
-                // positions 8 kg .. 8 kg + 7 of either plane = channels {4 kg ..} and {16 + 4 kg ..} (engine.SPLIT_PAIR_PERM)
-                const float o = ((float)resh[ph][nh * 4 + e] + (float)resl[ph][nh * 4 + e]) * inv_a;
-                v[e] = fmaxf(acc[0][ph][nh][e] * out_scale + bq[0][nh][e], 0.f) + fmaxf(acc[1][ph][nh][e] * out_scale + bq[1][nh][e], 0.f) +
-                       fmaxf(acc[2][ph][nh][e] * out_scale + bq[2][nh][e], 0.f) + o;        // o + o1 + o2 + o3 (bdcn_new.py:54)
-                sc[0][ph] += v[e] * cwq[0][nh][e];
-                sc[1][ph] += v[e] * cwq[1][nh][e];
-                if (nh == 0 && e == 0) ovf_bad |= egne_nonfinite(acc[0][ph][nh][e] + acc[1][ph][nh][e] + acc[2][ph][nh][e] + o);
-              }
-              if (p.out) {
-                const int n = nh * 16 + 4 * kg;
-                const int oo = (okp && n < p.Cout_store) ? (pix * (int)p.out_pix_stride + p.out_ch_off + n) * 4 : (int)OOB;
-                __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), rout, oo, 0, 0);
-              }
-            }
+            okp[ph] = R < Hp && Cq < Wp;
+            pix[ph] = y * W + x;
           }
-          if (score_w) {
-#pragma unroll
-            for (int h = 0; h < 2; ++h)
-#pragma unroll
-              for (int ph = 0; ph < NPH; ++ph) {
-                float tt = sc[h][ph];
-                tt += __shfl_xor(tt, 16);
-                tt += __shfl_xor(tt, 32);
-                sc[h][ph] = tt;
-              }
-            const int h = kg >> 1, ph = kg & 1;
-            const float v = h ? (ph ? sc[1][1] : sc[1][0]) : (ph ? sc[0][1] : sc[0][0]);
-            if (sdst) *sdst = v + (accumulate ? sprev : lconst[160 + h]);
-          }
+          msdil_epilogue<NPH, true>(p, lconst, acc, resh, resl, pix, okp, rout, inv_a, out_scale, kg, score_w, sdst, sprev, accumulate, ovf_bad);
         };
 
         // sub-step S: [weights of S + 2 -> LDS] [S = 0: the next 8 rows -> the free ring group] [36 MFMAs] [wait for the weights of
@@ -303,9 +241,8 @@ void msdil3_kernel(const egne_conv_desc p, const _Float16* __restrict__ fhi, con
             if constexpr (S == 0) issue_group(y0 + 2 * TH - HALO, gnext, more);
             if constexpr (S == NS - 1) {
               // the running score sums (lane (l15, kg) finishes head kg >> 1 of pixel block kg & 1); unconditional load
-              const int h = kg >> 1, R = y0 + wave, Cq = C0 + (kg & 1) * 16 + l15;
-              sdst = (score_w && R < Hp && Cq < Wp) ? (h ? s1 : s0) + ((long long)b * H + 4 * R + py) * W + 4 * Cq + px : nullptr;
-              sprev = *(sdst ? (const volatile float*)sdst : (const volatile float*)p.residual);
+              const int R = y0 + wave, Cq = C0 + (kg & 1) * 16 + l15;
+              msdil_score_prefetch(p, score_w, s0, s1, kg, b, 4 * R + py, 4 * Cq + px, R < Hp && Cq < Wp, sdst, sprev);
             }
             compute(std::integral_constant<int, S>{});
             // S = 8: everything, i.e. the weights of the next step's sub-steps 0 AND 1 (a sub-step old) and the score load, in front
@@ -341,40 +278,22 @@ bool msdil3_wanted(const egne_conv_desc& d) {
   return !(e && atoi(e) == 0) && d.f16_products != 1 && d.seg[0].presplit == 1 && d.W >= 64 && d.H >= 48;
 }
 
-// Segments per plane column: a column is cut where whole columns would leave compute units without work; each segment pays about one
-// step for its two exposed ring groups.  EGNE_MSDIL3_SEGS = 1..4 (read per launch) forces a count (tests).
-void msdil3_items(int B, int H, int W, int force, int* ncols, int* nseg, int* seg_rows, long long* nitems) {
-  const int Hp = (H + 3) / 4, Wp = (W + 3) / 4;              // the largest plane (phase 0, 0)
-  *ncols = (Wp + TW - 1) / TW;
-  int best = 1;
-  double best_t = 1e30;
-  for (int ns = 1; ns <= 4; ++ns) {
-    const int rows = ((Hp + ns - 1) / ns + TH - 1) / TH * TH;
-    if (ns > 1 && rows * (ns - 1) >= Hp) continue;            // an empty last segment
-    const long long items = (long long)B * 16 * *ncols * ns;
-    const double t = (double)((items + 255) / 256) * (rows / TH + 1.0);
-    if (force == ns) { best = ns; break; }
-    if (t < best_t) { best_t = t; best = ns; }
-  }
-  *nseg = best;
-  *seg_rows = ((Hp + best - 1) / best + TH - 1) / TH * TH;
-  *nitems = (long long)B * 16 * *ncols * best;
-}
-
-// Called by msdil_ps_launch for three-product operands on maps of 48 x 64 and larger; the descriptor has been validated by
-// egne_msblock_dil_scores_f16_fwd.
+// Called by egne_msblock_dil_scores_f16_fwd, which has validated the descriptor, for three-product operands on maps of 48 x 64 and
+// larger.  Work items: (frame, phase, 32-pixel plane column, vertical segment), sized by the largest plane (phase 0, 0); a segment pays
+// about one step for its two exposed ring groups.  EGNE_MSDIL3_SEGS = 1..4 (read per launch) forces a segment count (tests).
 int msdil3_launch(const egne_conv_desc& d, const void* fhi, const void* flo, float a_scale, float w_scale, const float* score_w,
                   const float* score_c, float* s0, float* s1, int accumulate, hipStream_t st) {
+  static_assert(TH == 8, "msdil_segments counts steps of 8 rows");
   const char* e = getenv("EGNE_MSDIL3_SEGS");
-  int ncols, nseg, seg_rows;
-  long long nitems;
-  msdil3_items(d.B, d.H, d.W, e ? atoi(e) : 0, &ncols, &nseg, &seg_rows, &nitems);
+  const int Hp = (d.H + 3) / 4, Wp = (d.W + 3) / 4, ncols = (Wp + TW - 1) / TW;
+  const msdil_segs sg = msdil_segments(Hp, (long long)d.B * 16 * ncols, 1.0, e ? atoi(e) : 0);
+  const long long nitems = (long long)d.B * 16 * ncols * sg.nseg;
   if (nitems > 0x7fffffff - 256) return egne::fail(EGNE_ERR_ARG, "msblock_dil (phase-plane ring): %lld work items", nitems);
   if (!egne::raise_lds((const void*)msdil3_kernel, LDS_BYTES))
     return egne::fail(EGNE_ERR_LAUNCH, "msblock_dil (phase-plane ring): cannot raise the dynamic LDS limit to %d", LDS_BYTES);
-  const float os = 1.0f / (a_scale * w_scale), inv_a = 1.0f / a_scale;
+  const msdil_scales sc = msdil_scales_of(a_scale, w_scale);
   hipLaunchKernelGGL(msdil3_kernel, dim3((unsigned)(nitems < 256 ? nitems : 256)), dim3(512), LDS_BYTES, st, d, (const _Float16*)fhi,
-                     (const _Float16*)flo, inv_a, os, ncols, nseg, seg_rows, (int)nitems, score_w, score_c, s0, s1, accumulate);
+                     (const _Float16*)flo, sc.inv_a, sc.os, ncols, sg.nseg, sg.seg_rows, (int)nitems, score_w, score_c, s0, s1, accumulate);
   return egne::check_launch("egne_msblock_dil_f16_fwd (phase-plane ring)");
 }
 

@@ -18,33 +18,16 @@
 //             ninth strip bias + ReLU per dilation, the three are summed, the exact fp32 o is added and the tile stored.
 // One s_barrier per strip.  The conversion work (each element is split 9 times) sits in waves that do nothing else.
 #include "common.h"
+#include "kernel_util.h"
+#include "msblock_dil_common.h"      // (the launchers of the family's other kernels; this kernel has an epilogue of its own)
 #include "split_f16.h"
 #include <type_traits>
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef _Float16 h8 __attribute__((ext_vector_type(8)));
-typedef _Float16 h4 __attribute__((ext_vector_type(4)));
-typedef _Float16 h2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
 namespace {
 __device__ int g_mdbg = 0;
 __device__ unsigned long long g_mstamps[256 * 8 * 4];
 
 constexpr int TW = 32, TH = 8;
-constexpr unsigned OOB = 0x80000000u;
-
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const void* base, unsigned bytes) {
-  return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), 0, (int)bytes, 0x00020000);
-}
-
-__device__ __forceinline__ void lds_barrier() {
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  __builtin_amdgcn_s_barrier();
-  asm volatile("" ::: "memory");
-}
 
 // XIN: this launch holds only tiles whose widest strip lies inside the image columns (x0 >= 12, x0 + 32 + 12 <= W): item addresses
 // are then a per-lane constant + a wave-uniform term.  A map is covered by an XIN launch over the interior tile columns and a
@@ -403,19 +386,26 @@ extern "C" int egne_msblock_dil_scores_f16_fwd(const egne_conv_desc* dp, const v
   const int tiles_x = (d.W + TW - 1) / TW, tiles_y = (d.H + TH - 1) / TH;
   const int ntiles = tiles_x * tiles_y * d.B;
   constexpr size_t lds = ((size_t)2 * 2 * TH * (TW + 24) * 32 + 2 * 12 * 512) * sizeof(_Float16);
-  static bool once = hipFuncSetAttribute((const void*)msblock_dil_kernel<4, 8, 12, 4, false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) == hipSuccess &&
-                     hipFuncSetAttribute((const void*)msblock_dil_kernel<4, 8, 12, 4, true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) == hipSuccess &&
-                     hipFuncSetAttribute((const void*)msblock_dil_kernel<4, 8, 12, 4, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) == hipSuccess &&
-                     hipFuncSetAttribute((const void*)msblock_dil_kernel<4, 8, 12, 4, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) == hipSuccess;
-  if (!once) return egne::fail(EGNE_ERR_LAUNCH, "msblock_dil: cannot raise the dynamic LDS limit to %zu", lds);
-  const float os = 1.0f / (a_scale * w_scale), inv_a = 1.0f / a_scale;
+  if (!egne::raise_lds_all(lds, msblock_dil_kernel<4, 8, 12, 4, false, false>, msblock_dil_kernel<4, 8, 12, 4, true, false>,
+                           msblock_dil_kernel<4, 8, 12, 4, false, true>, msblock_dil_kernel<4, 8, 12, 4, true, true>))
+    return egne::fail(EGNE_ERR_LAUNCH, "msblock_dil: cannot raise the dynamic LDS limit to %zu", lds);
+  const egne::msdil_scales scl = egne::msdil_scales_of(a_scale, w_scale);
+  const float os = scl.os, inv_a = scl.inv_a;
   EGNE_REQUIRE((g.presplit == 0 || g.presplit == 1) && d.out_split == 0, "msblock_dil: presplit %d / out_split %d: the input is fp32 or split-pair storage 1, the output fp32", g.presplit, d.out_split);
   const bool ps = g.presplit != 0;
   // split-pair input: the residual must be that same slice (bdcn_new.py:54 adds `o` itself), whole 32-channel blocks
   EGNE_REQUIRE(!ps || (d.residual == g.ptr && d.res_pix_stride == g.pix_stride && d.res_ch_off == g.ch_off && g.ch_off % 32 == 0),
                "msblock_dil: a split-pair input must also be the residual");
   static const bool ps_sym = getenv("EGNE_MSDIL_PS_OLD") == nullptr;      // (diagnostics: the producer / consumer kernel with copying producers)
-  if (ps && ps_sym) return egne::msdil_ps_launch(d, fhi, flo, a_scale, w_scale, score_w, score_c, s0, s1, accumulate, (hipStream_t)stream);
+  // ---- the ONE place that picks the form.  Split-pair input: plain-f16 ring, phase-plane ring, strip kernel (each launcher says what it
+  // takes: msdil1_wanted / msdil3_wanted, EGNE_MSDIL1 / EGNE_MSDIL3 read at every launch); fp32 input, or EGNE_MSDIL_PS_OLD: the producer /
+  // consumer kernel of this file
+  if (ps && ps_sym) {
+    hipStream_t st = (hipStream_t)stream;
+    if (egne::msdil1_wanted(d)) return egne::msdil1_launch(d, fhi, a_scale, w_scale, score_w, score_c, s0, s1, accumulate, st);
+    if (egne::msdil3_wanted(d)) return egne::msdil3_launch(d, fhi, flo, a_scale, w_scale, score_w, score_c, s0, s1, accumulate, st);
+    return egne::msdil_ps_launch(d, fhi, flo, a_scale, w_scale, score_w, score_c, s0, s1, accumulate, st);
+  }
   auto launch = [&](auto xin, int grid, int nt, int cols) {
     constexpr bool XIN = decltype(xin)::value;
     if (ps) hipLaunchKernelGGL((msblock_dil_kernel<4, 8, 12, 4, XIN, true>), dim3(grid), dim3(512), lds, (hipStream_t)stream, d, (const _Float16*)fhi,

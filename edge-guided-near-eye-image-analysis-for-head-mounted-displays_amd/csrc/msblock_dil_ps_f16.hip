@@ -20,12 +20,9 @@
 // multiple of 128 so that the eight lanes of a pixel (4 hi + 4 lo chunks) write 128 distinct bank bytes -- and the strip's 12 weight
 // fragments in one of two weight buffers.  One s_barrier per strip.
 #include "common.h"
+#include "kernel_util.h"
+#include "msblock_dil_common.h"
 #include <type_traits>
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 h8 __attribute__((ext_vector_type(8)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(3))) void* lds_ptr;
 
 namespace {
 __device__ int g_pdbg = 0;
@@ -38,17 +35,6 @@ constexpr int PLANE = NPXMAX * 32 + 32;                        // halfs per plan
 constexpr int BUFH = 2 * PLANE;                                // halfs per strip buffer
 constexpr int WBUFH = 12 * 512;                                // halfs per weight buffer: [kx 3][ks 2][hi | lo][64 lanes][8]
 constexpr int NS = 9;
-constexpr unsigned OOB = 0x80000000u;
-
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const void* base, unsigned bytes) {
-  return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), 0, (int)bytes, 0x00020000);
-}
-
-__device__ __forceinline__ void lds_barrier() {
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  __builtin_amdgcn_s_barrier();
-  asm volatile("" ::: "memory");
-}
 
 constexpr int dil_of(int g) { return g == 0 ? D0 : (g == 1 ? D1 : D2); }
 constexpr int ni_of(int g) { return TH * (TW + 2 * dil_of(g)) * 8 / 512; }     // 16-byte items per lane and strip: 5 / 6 / 7 (exact)
@@ -97,12 +83,7 @@ void msdil_ps_kernel(const egne_conv_desc p, const _Float16* __restrict__ fhi, c
   };
   int nmine = 0;
   while (tile_at(nmine) < ntiles) ++nmine;
-  if (tid < 160) {
-    const int r = tid >> 5, c = tid & 31;
-    lconst[tid] = r < 3 ? (p.bias ? p.bias[r * p.CoutP + c] : 0.f) : (score_w ? score_w[(r - 3) * 32 + c] : 0.f);
-  } else if (tid < 162) {
-    lconst[tid] = score_c ? score_c[tid - 160] : 0.f;
-  }
+  msdil_fill_lconst(lconst, tid, p, score_w, score_c);
 
   // ---- copy side: strip items.  Item I of a lane: pixel (tid >> 3) + 64 I of the strip (row-major over 8 x SW), 16-byte piece tid & 7
   // of its 128 bytes: pieces 0-3 = chunks of the hi plane, 4-7 = of the lo plane.
@@ -238,68 +219,23 @@ void msdil_ps_kernel(const egne_conv_desc p, const _Float16* __restrict__ fhi, c
   float* sdst = nullptr;
   float sprev = 0.f;
   bool ovf_bad = false;
-  auto score_prefetch = [&](const Tile& tl) {      // lane (l15, kg) finishes head kg >> 1 of pixel block kg & 1
-    const int h = kg >> 1, y = tl.y0 + wave, x = tl.x0 + (kg & 1) * 16 + l15;
-    sdst = (score_w && y < H && x < W) ? (h ? s1 : s0) + ((long long)tl.b * H + y) * W + x : nullptr;
-    sprev = *(sdst ? (const volatile float*)sdst : (const volatile float*)p.residual);     // unconditional: the load counter below counts instructions
+  auto score_prefetch = [&](const Tile& tl) {      // (unconditional load: the load counter below counts instructions)
+    const int y = tl.y0 + wave, x = tl.x0 + (kg & 1) * 16 + l15;
+    msdil_score_prefetch(p, score_w, s0, s1, kg, tl.b, y, x, y < H && x < W, sdst, sprev);
   };
   auto epilogue = [&](const Tile& tl) {
     const int y = tl.y0 + wave;
     const __amdgpu_buffer_rsrc_t rout = make_rsrc(p.out ? p.out + (long long)tl.b * H * W * p.out_pix_stride : nullptr, p.out ? frame_out : 0u);
-    f32x4 bq[3][2], cwq[2][2];
-#pragma unroll
-    for (int nh = 0; nh < 2; ++nh) {
-      const int n = nh * 16 + 4 * kg;
-#pragma unroll
-      for (int g = 0; g < 3; ++g) bq[g][nh] = *(const f32x4*)&lconst[g * 32 + n];
-#pragma unroll
-      for (int h = 0; h < 2; ++h) cwq[h][nh] = *(const f32x4*)&lconst[(3 + h) * 32 + n];
-    }
-    float sc[2][2];                                      // [head][ph]
+    int pix[2];
+    bool okp[2];
 #pragma unroll
     for (int ph = 0; ph < 2; ++ph) {
       const int x = tl.x0 + ph * 16 + l15;
-      const bool okp = y < H && x < W;
-      const int pix = y * W + x;
-      sc[0][ph] = sc[1][ph] = 0.f;
-#pragma unroll
-      for (int nh = 0; nh < 2; ++nh) {
-        f32x4 v;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          // positions 8 kg .. 8 kg + 7 of either plane = channels {4 kg ..} and {16 + 4 kg ..} (engine.SPLIT_PAIR_PERM)
-          const float o = ((float)resh[ph][nh * 4 + e] + (float)resl[ph][nh * 4 + e]) * inv_a;
-          v[e] = fmaxf(acc[0][ph][nh][e] * out_scale + bq[0][nh][e], 0.f) + fmaxf(acc[1][ph][nh][e] * out_scale + bq[1][nh][e], 0.f) +
-                 fmaxf(acc[2][ph][nh][e] * out_scale + bq[2][nh][e], 0.f) + o;        // o + o1 + o2 + o3 (bdcn_new.py:54)
-          sc[0][ph] += v[e] * cwq[0][nh][e];
-          sc[1][ph] += v[e] * cwq[1][nh][e];
-          // (fmaxf(x, 0) swallows NaN and -inf: the overflow test takes the accumulators themselves; lane = pixel: one channel per
-          //  pixel, common.h)
-          if (nh == 0 && e == 0) ovf_bad |= egne_nonfinite(acc[0][ph][nh][e] + acc[1][ph][nh][e] + acc[2][ph][nh][e] + o);
-        }
-        if (p.out) {
-          const int n = nh * 16 + 4 * kg;
-          const int oo = (okp && n < p.Cout_store) ? (pix * (int)p.out_pix_stride + p.out_ch_off + n) * 4 : (int)OOB;
-          __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), rout, oo, 0, 0);
-        }
-      }
+      okp[ph] = y < H && x < W;
+      pix[ph] = y * W + x;
     }
-    if (score_w) {
-      // this block's share of the stage's two score maps (bdcn_new.py:118-166 is linear behind the block: per block and head ONE
-      // 32-vector): 8 channels were summed in the lane, the other 24 sit in lanes l15 + 16, + 32, + 48 -- two exchanges, fixed order
-#pragma unroll
-      for (int h = 0; h < 2; ++h)
-#pragma unroll
-        for (int ph = 0; ph < 2; ++ph) {
-          float t = sc[h][ph];
-          t += __shfl_xor(t, 16);
-          t += __shfl_xor(t, 32);
-          sc[h][ph] = t;
-        }
-      const int h = kg >> 1, ph = kg & 1;
-      const float v = h ? (ph ? sc[1][1] : sc[1][0]) : (ph ? sc[0][1] : sc[0][0]);
-      if (sdst) *sdst = v + (accumulate ? sprev : lconst[160 + h]);
-    }
+    // (NP == 1: the lo halves of the centre tap were read as zeros)
+    msdil_epilogue<2, true>(p, lconst, acc, resh, resl, pix, okp, rout, inv_a, out_scale, kg, score_w, sdst, sprev, accumulate, ovf_bad);
   };
 
   __syncthreads();                  // lconst / lrel
@@ -358,23 +294,21 @@ void msdil_ps_kernel(const egne_conv_desc p, const _Float16* __restrict__ fhi, c
 }  // namespace
 
 namespace egne {
-// Called by egne_msblock_dil_scores_f16_fwd (msblock_dil_f16.hip) for a descriptor whose input slice is in split-pair storage; the
-// descriptor has been validated there.
+// The strip kernel.  Called by egne_msblock_dil_scores_f16_fwd (msblock_dil_f16.hip), which has validated the descriptor, for an input
+// slice in split-pair storage that neither ring kernel takes.
 int msdil_ps_launch(const egne_conv_desc& d, const void* fhi, const void* flo, float a_scale, float w_scale, const float* score_w,
                     const float* score_c, float* s0, float* s1, int accumulate, hipStream_t st) {
-  if (msdil1_wanted(d)) return msdil1_launch(d, fhi, a_scale, w_scale, score_w, score_c, s0, s1, accumulate, st);
-  if (msdil3_wanted(d)) return msdil3_launch(d, fhi, flo, a_scale, w_scale, score_w, score_c, s0, s1, accumulate, st);
   const int tiles_x = (d.W + TW - 1) / TW, tiles_y = (d.H + TH - 1) / TH;
   const int ntiles = tiles_x * tiles_y * d.B;
   constexpr size_t lds = ((size_t)2 * BUFH + 2 * WBUFH) * sizeof(_Float16) + 162 * sizeof(float) + 18 * 64 * sizeof(int) + WBUFH * sizeof(_Float16);
   static_assert(lds <= 163840, "LDS budget");
-  const float os = 1.0f / (a_scale * w_scale), inv_a = 1.0f / a_scale;
+  const msdil_scales sc = msdil_scales_of(a_scale, w_scale);
+  const float os = sc.os, inv_a = sc.inv_a;
   const bool split = tiles_x > 2 && d.W >= TW * (tiles_x - 1) + 12;
   auto go = [&](auto npc) -> int {
     constexpr int NP = decltype(npc)::value;
-    static bool once = hipFuncSetAttribute((const void*)msdil_ps_kernel<false, NP>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) == hipSuccess &&
-                       hipFuncSetAttribute((const void*)msdil_ps_kernel<true, NP>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) == hipSuccess;
-    if (!once) return egne::fail(EGNE_ERR_LAUNCH, "msblock_dil (split-pair input): cannot raise the dynamic LDS limit to %zu", lds);
+    if (!egne::raise_lds_all(lds, msdil_ps_kernel<false, NP>, msdil_ps_kernel<true, NP>))
+      return egne::fail(EGNE_ERR_LAUNCH, "msblock_dil (split-pair input): cannot raise the dynamic LDS limit to %zu", lds);
     if (split) {
       const int nt_in = (tiles_x - 2) * tiles_y * d.B, nt_b = 2 * tiles_y * d.B;
       hipLaunchKernelGGL((msdil_ps_kernel<true, NP>), dim3(nt_in < 256 ? nt_in : 256), dim3(512), lds, st, d, (const _Float16*)fhi, (const _Float16*)flo,

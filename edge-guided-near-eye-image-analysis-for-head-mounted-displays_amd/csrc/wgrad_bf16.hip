@@ -14,12 +14,8 @@
 // The optional per-(n, c) affine + activation of the forward launch (InstanceNorm fused on load) is applied while staging x.
 // Partials: ws[split][tap][CoutP][Ktot] fp32, every element written (the caller reduces them into the OIHW gradient).
 #include "common.h"
+#include "kernel_util.h"
 #include <cstdlib>
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
 
 namespace {
 
@@ -27,12 +23,8 @@ constexpr int TW = 32, TH = 8, HWd = TW + 2, HHd = TH + 2, NPX = HHd * HWd;     
 constexpr int GPX = TW * TH;                                                      // 256 gz pixels
 constexpr int NT = 512;                                                           // threads: eight waves, one tile row each
 constexpr int NG = GPX * 4 / NT, NX = (NPX * 4 + NT - 1) / NT;                   // 16-byte items per thread: 2 + 3
-constexpr unsigned OOB = 0x80000000u;
 typedef __attribute__((address_space(3))) egne_bf16x4* lds_bf4_ptr;
 
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const void* base, unsigned bytes) {
-  return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), 0, (int)bytes, 0x00020000);
-}
 __device__ __forceinline__ f32x4 unpack4(unsigned a, unsigned b) {
   const u32x4 w = {a << 16, a & 0xffff0000u, b << 16, b & 0xffff0000u};
   return __builtin_bit_cast(f32x4, w);

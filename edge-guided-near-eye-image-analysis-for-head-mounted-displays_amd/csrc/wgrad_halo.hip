@@ -12,25 +12,17 @@
 // stay in registers across tiles; at the end the four waves are summed through LDS and the block writes its partial
 // to ws[split][tap][CoutP][Ktot], the layout egne_conv2d_wgrad's deterministic reduce expects.
 #include "common.h"
+#include "kernel_util.h"
 #include "split_f16.h"
 #include <cstdlib>
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 h2 __attribute__((ext_vector_type(2)));
 
 namespace {
 
-constexpr unsigned OOB = 0x80000000u;
 constexpr int TH = 8, TW = 32, HW_ = TW + 2, HH_ = TH + 2, NPX = HH_ * HW_;   // 340 halo pixels
 constexpr int NX = (NPX * 8 + 255) / 256;                                     // 11 x items (float4) per thread
 constexpr int NG = TH * TW * 8 / 256;                                         // 8 gz items per thread
-
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const void* base, unsigned bytes) {
-  return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), 0, (int)bytes, 0x00020000);
-}
 
 __global__ __launch_bounds__(256, 2) void conv3x3_wgrad_halo_kernel(const egne_conv_desc p, const float* __restrict__ gz, long long gzs,
                                                                     int gzo, int tiles_x, int tiles_y, int ntiles, int nchunk,
@@ -402,10 +394,7 @@ int wgrad_halo_launch(const egne_conv_desc& d, const float* gz, long long gzs, i
   const int nchunk = (d.seg[0].Cp + 31) / 32;
   const int gx = wgrad_halo_splits(d);
   const size_t lds = (size_t)(NPX + TH * TW) * 32 * sizeof(float);
-  static bool once = [] {
-    return hipFuncSetAttribute((const void*)conv3x3_wgrad_halo_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024) == hipSuccess;
-  }();
-  if (!once) return fail(EGNE_ERR_LAUNCH, "wgrad_halo: cannot raise the dynamic LDS limit");
+  if (!raise_lds((const void*)conv3x3_wgrad_halo_kernel, 80 * 1024)) return fail(EGNE_ERR_LAUNCH, "wgrad_halo: cannot raise the dynamic LDS limit");
   hipLaunchKernelGGL(conv3x3_wgrad_halo_kernel, dim3(gx, (d.CoutP / 32) * nchunk), dim3(256), lds, st, d, gz, gzs, gzo, tiles_x, tiles_y,
                      ntiles, nchunk, ws);
   return check_launch("conv3x3_wgrad_halo");
@@ -420,10 +409,7 @@ int wgrad_halo_f16_launch(const egne_conv_desc& d, const float* gz, long long gz
   const int nchunk = (d.seg[0].Cp + 31) / 32;
   const int gx = wgrad_halo_splits(d);
   const size_t lds = (size_t)(NPX + TH * TW) * 32 * sizeof(float);
-  static bool once = [] {
-    return hipFuncSetAttribute((const void*)conv3x3_wgrad_halo_f16_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024) == hipSuccess;
-  }();
-  if (!once) return fail(EGNE_ERR_LAUNCH, "wgrad_halo_f16: cannot raise the dynamic LDS limit");
+  if (!raise_lds((const void*)conv3x3_wgrad_halo_f16_kernel, 80 * 1024)) return fail(EGNE_ERR_LAUNCH, "wgrad_halo_f16: cannot raise the dynamic LDS limit");
   hipLaunchKernelGGL(conv3x3_wgrad_halo_f16_kernel, dim3(gx, (d.CoutP / 32) * nchunk), dim3(256), lds, st, d, gz, gzs, gzo, gz_dyn,
                      tiles_x, tiles_y, ntiles, nchunk, ws);
   return check_launch("conv3x3_wgrad_halo_f16");

@@ -1,8 +1,11 @@
 #!/bin/bash
-# A/B of the overflow tests in the split-f16 epilogues: the same tree built with -DEGNE_NO_OVF_CHECK (scratch/novf_build) against the
-# in-tree library, alternating, inference leg with and without the two-stage pipeline
+# A/B of the overflow tests in the split-f16 epilogues: the same sources built with -DEGNE_NO_OVF_CHECK into build/novf (ignored by git)
+# against the in-tree library, alternating, inference leg with and without the two-stage pipeline.  The second library, from the
+# repository root:
+#   make -C edge-guided-near-eye-image-analysis-for-head-mounted-displays_amd/csrc -j8 OBJDIR=$PWD/build/novf EXTRA_CXXFLAGS=-DEGNE_NO_OVF_CHECK
 R=$GRAFT_REPO_ROOT; out=$R/gpurun_out/${1:-ab_ovf}; mkdir -p $out
-P=$R/scratch/novf_build/edge-guided-near-eye-image-analysis-for-head-mounted-displays_amd/csrc/libegne_hip.so
+P=${NOVF_LIB:-$R/build/novf/libegne_hip.so}
+[ -f "$P" ] || { echo "no library at $P: build it first (header of this script)" >&2; exit 1; }
 for i in 1 2 3; do
   EGNE_LIB=$P python3 $R/bench.py --mode infer --steps 20 --warmup 5 --no-cpu-baseline > $out/novf_$i.json 2> $out/novf_$i.err
   python3 $R/bench.py --mode infer --steps 20 --warmup 5 --no-cpu-baseline > $out/ovf_$i.json 2> $out/ovf_$i.err
