@@ -130,6 +130,8 @@ SIGNATURES = {
     "egne_affine_act": (i32, [vp, i64, i32, vp, i64, i32, i32, i64, vp, vp, i32, vp]),
     "egne_augment": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, vp]),
     "egne_augment_cv": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, vp]),
+    "egne_loader_stage": (i32, [vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+    "egne_loader_finish": (i32, [vp, vp, vp, vp, i32, i32, vp]),
     "egne_conv3x3_smallcin_f16_fwd": (i32, [C.POINTER(ConvDesc), vp, vp, f32, f32, vp]),
     "egne_pack_conv3x3_c4_weight_f16": (i32, [vp, i32, i32, i32, f32, vp, vp, vp]),
     "egne_conv1x1_ms_f16x3_fwd": (i32, [C.POINTER(ConvDesc), vp, vp, f32, f32, vp]),

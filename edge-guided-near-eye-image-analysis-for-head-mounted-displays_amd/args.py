@@ -48,6 +48,12 @@ _DATA = (
                             "(parity unpinned: restated from OpenCV's published Canny / dilate); 3: pupil_center, elNorm and cond "
                             "too, from the reference's ElliFit + RANSAC on the label's boundaries (egne_amd.dataprep.ellipse_targets): "
                             "(image, label) pairs are then enough"),
+    ("device_loader", int, 0, "1: the Dataset hands out RAW samples (uint8 image, stored label, ellipses) and every batch is prepared on "
+                              "the GPU (egne_amd.loader.device_batch: pad, augmentation -- training only --, label remap, z-score, "
+                              "weights, distance maps, ellipse normalisation); --synthetic N then uses SyntheticRawEyes, otherwise "
+                              "--raw_archive names the data"),
+    ("raw_archive", str, None, "with --device_loader 1: an .npz with the arrays of the reference's H5 archives (Images, Masks_noSkin, "
+                               "pupil_loc, Fits_pupil, Fits_iris; egne_amd.loader.RawArchive)"),
 )
 _OUTPUT = (
     ("expname", str, "dev", "sub-directory of logs/<model>/"),
@@ -74,7 +80,9 @@ def build_parser():
 
 def parse_args(argv=None):
     args = build_parser().parse_args(argv)
-    if args.curObj is None and not args.synthetic:
+    if args.device_loader and not args.synthetic and not args.raw_archive:
+        raise SystemExit('--device_loader 1 needs --raw_archive PATH (or --synthetic N)')
+    if args.curObj is None and not args.synthetic and not (args.device_loader and args.raw_archive):
         raise SystemExit('--curObj is required (or use --synthetic N)')
     print('------')
     print('parsed arguments:')

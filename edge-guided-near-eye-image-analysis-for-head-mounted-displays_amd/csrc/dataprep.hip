@@ -10,6 +10,7 @@
 // Integer arithmetic up to the final double sqrt / divide, so the float32 result is bit-identical to the reference's.
 // Quirk kept: for a class that fills the whole frame scipy measures to a virtual background pixel at (-1, 0).
 #include "common.h"
+#include "zscore_core.h"
 
 namespace {
 
@@ -66,7 +67,7 @@ __global__ void edt_rows_k(const long long* __restrict__ label, int H, int W, in
     if (fl & 1) {                                   // class present in this frame
       const bool in = in_row[x];
       if (in && !(fl & 2)) {
-        res = -(sqrt((double)((y + 1) * (y + 1) + x * x)) - 1.0);           // scipy: no background anywhere
+        res = 1.0 - sqrt((double)((y + 1) * (y + 1) + x * x));              // scipy: no background anywhere
       } else {
         const unsigned short* gv = in ? row : row + W;                      // inside: distance to the outside, and vice versa
         int best = 0x7fffffff;
@@ -78,7 +79,7 @@ __global__ void edt_rows_k(const long long* __restrict__ label, int H, int W, in
           }
         }
         const double dist = sqrt((double)best);
-        res = in ? -(dist - 1.0) : dist;
+        res = in ? 1.0 - dist : dist;          // (not -(dist - 1.0): the reference's 0 - (1 - 1) one pixel inside the boundary is +0.0)
       }
     }
     o[x] = (float)(res / mx);
@@ -90,19 +91,8 @@ __global__ __launch_bounds__(256) void zscore_k(const float* __restrict__ x, flo
   __shared__ double sh[256];
   const float* xi = x + (long long)blockIdx.x * n;
   float* yi = y + (long long)blockIdx.x * n;
-  double s = 0;
-  for (int i = threadIdx.x; i < n; i += 256) s += xi[i];
-  sh[threadIdx.x] = s;
-  __syncthreads();
-  for (int k = 128; k >= 1; k >>= 1) { if ((int)threadIdx.x < k) sh[threadIdx.x] += sh[threadIdx.x + k]; __syncthreads(); }
-  const double mean = sh[0] / n;
-  __syncthreads();
-  double q = 0;
-  for (int i = threadIdx.x; i < n; i += 256) { const double d = xi[i] - mean; q += d * d; }
-  sh[threadIdx.x] = q;
-  __syncthreads();
-  for (int k = 128; k >= 1; k >>= 1) { if ((int)threadIdx.x < k) sh[threadIdx.x] += sh[threadIdx.x + k]; __syncthreads(); }
-  const double sd = sqrt(sh[0] / n);
+  double mean, sd;
+  egne::zscore_stats([=](int i) { return xi[i]; }, n, sh, mean, sd);      // zscore_core.h, shared with csrc/loader.hip
   for (int i = threadIdx.x; i < n; i += 256) yi[i] = (float)((xi[i] - mean) / sd);
 }
 

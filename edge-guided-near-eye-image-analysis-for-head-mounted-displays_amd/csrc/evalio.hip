@@ -4,7 +4,7 @@
 // plot_segmap_ellpreds / _draw_ellipse, the edge frame of draw()); this file is compiled without FMA contraction (Makefile).
 //
 // egne_eval_prep:   [lanczos_k]  ->  sums_k  ->  normalise_k
-//   lanczos_k    one workgroup per output row of an eye: the 8-tap row pass of that row in float64 into LDS (sequential sum, as NumPy
+//   lanczos_k    (resample_core.h, shared with csrc/loader.hip) one workgroup per output row of an eye: the 8-tap row pass of that row in float64 into LDS (sequential sum, as NumPy
 //                reduces a middle axis), then the 8-tap column pass out of LDS (pairwise sum, as NumPy reduces a contiguous axis of 8),
 //                rint + clip to uint8.  Tap indices and weights come from the host's tables (same bits as resize_lanczos4's).
 //   sums_k       one workgroup per eye: S = sum(x), Q = sum(x*x) in 64-bit integers over the rows that survive the centre crop
@@ -12,6 +12,7 @@
 //   normalise_k  mean = S / n, std = sqrt(n*Q - S*S) / n in float64, out = float((x - mean) / std); padding rows are (0 - mean) / std.
 // egne_eval_render: render_k -> outline_k (iris) -> outline_k (pupil); three launches on one stream, so later writes win.
 #include "common.h"
+#include "resample_core.h"
 
 namespace {
 
@@ -22,8 +23,6 @@ struct EyeView {          // where eye e's uint8 image lives: base + (e / eyes) 
   __device__ __forceinline__ const uint8_t* at(int e) const { return base + (long long)(e / eyes) * frame_stride + (long long)(e % eyes) * eye_stride; }
 };
 
-__device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
-
 // grid (Hr, E), 256 threads, dynamic LDS: We doubles
 __global__ __launch_bounds__(256) void lanczos_k(EyeView src, int Hs, int We, int Hr, int Wr, const int* __restrict__ ridx,
                                                  const double* __restrict__ rw, const int* __restrict__ cidx,
@@ -31,33 +30,9 @@ __global__ __launch_bounds__(256) void lanczos_k(EyeView src, int Hs, int We, in
   extern __shared__ double rowbuf[];
   const int y = blockIdx.x, e = blockIdx.y;
   const uint8_t* s = src.at(e);
-  if (ridx) {
-    int ri[8];
-    double w[8];
-    for (int k = 0; k < 8; ++k) { ri[k] = clampi(ridx[y * 8 + k], 0, Hs - 1); w[k] = rw[y * 8 + k]; }
-    for (int x = threadIdx.x; x < We; x += 256) {
-      double acc = (double)s[(long long)ri[0] * src.ld + x] * w[0];
-      for (int k = 1; k < 8; ++k) acc = acc + (double)s[(long long)ri[k] * src.ld + x] * w[k];
-      rowbuf[x] = acc;
-    }
-  } else {
-    for (int x = threadIdx.x; x < We; x += 256) rowbuf[x] = (double)s[(long long)y * src.ld + x];
-  }
-  __syncthreads();
-  uint8_t* o = out + ((long long)e * Hr + y) * Wr;
-  for (int x = threadIdx.x; x < Wr; x += 256) {
-    double v;
-    if (cidx) {
-      double p[8];
-      for (int k = 0; k < 8; ++k) p[k] = rowbuf[clampi(cidx[x * 8 + k], 0, We - 1)] * cw[x * 8 + k];
-      v = ((p[0] + p[1]) + (p[2] + p[3])) + ((p[4] + p[5]) + (p[6] + p[7]));
-    } else {
-      v = rowbuf[x];
-    }
-    v = rint(v);
-    v = v < 0.0 ? 0.0 : (v > 255.0 ? 255.0 : v);
-    o[x] = (uint8_t)(int)v;
-  }
+  const int ld = src.ld;
+  egne::lanczos4_row([=](int r, int x) { return s[(long long)r * ld + x]; }, Hs, We, Wr, y, ridx, rw, cidx, cw, rowbuf,
+                     out + ((long long)e * Hr + y) * Wr);
 }
 
 // grid (E), 1024 threads: stats[e] = {S, Q} over rows [r0, r0 + nr) x W columns of eye e.  vec: every row start is 4-byte aligned.

@@ -59,9 +59,9 @@ def _mat3(rows):
     return torch.stack([torch.stack(r, dim=-1) for r in rows], dim=-2)
 
 
-def _ellipse_info(param, H, W):
-    """get_ellipse_info(param, H, cond=False)[1] (helperfunctions.py:488-518) for param [...,5] float64: my_ellipse.transform with
-    H = [[2/W, 0, -1], [0, 2/H, -1], [0, 0, 1]], mat2param, and the axis swap that keeps param 3 >= param 2."""
+def _ellipse_transform(param, Hi):
+    """my_ellipse(param).transform(H)[0][:-1] (helperfunctions.py:25-33, :50-63, :102-129) for param [...,5] float64 through the
+    conic; ``Hi`` [3,3] is the INVERSE of H."""
     cx, cy, a, b, th = param.unbind(-1)
     one, zero = torch.ones_like(cx), torch.zeros_like(cx)
 
@@ -76,7 +76,6 @@ def _ellipse_info(param, H, W):
     Hr, Ht = rot(-th), trans(-cx, -cy)
     Q = _mat3([[1 / a ** 2, zero, zero], [zero, 1 / b ** 2, zero], [zero, zero, -one]])
     mat = T(Ht) @ T(Hr) @ Q @ Hr @ Ht
-    Hi = torch.tensor([[W / 2, 0, W / 2], [0, H / 2, H / 2], [0, 0, 1]], dtype=param.dtype, device=param.device)      # inverse of H
     m = Hi.T @ mat @ Hi
     qa, qb, qc, qd, qe = m[..., 0, 0], 2 * m[..., 0, 1], m[..., 1, 1], 2 * m[..., 0, 2], 2 * m[..., 1, 2]
     flat = qb.abs() <= 1e-40
@@ -86,6 +85,14 @@ def _ellipse_info(param, H, W):
     R2, T2 = rot(t2), trans(tx, ty)
     mn = T(R2) @ T(T2) @ m @ T2 @ R2
     major, minor = torch.sqrt(1 / mn[..., 0, 0]), torch.sqrt(1 / mn[..., 1, 1])
+    return torch.stack([tx, ty, major, minor, t2], dim=-1)
+
+
+def _ellipse_info(param, H, W):
+    """get_ellipse_info(param, H, cond=False)[1] (helperfunctions.py:488-518) for param [...,5] float64: my_ellipse.transform with
+    H = [[2/W, 0, -1], [0, 2/H, -1], [0, 0, 1]], mat2param, and the axis swap that keeps param 3 >= param 2."""
+    Hi = torch.tensor([[W / 2, 0, W / 2], [0, H / 2, H / 2], [0, 0, 1]], dtype=param.dtype, device=param.device)      # inverse of H
+    tx, ty, major, minor, t2 = _ellipse_transform(param, Hi).unbind(-1)
     swap = major > minor
     return torch.stack([tx, ty, torch.where(swap, minor, major), torch.where(swap, major, minor),
                         torch.where(swap, 0.5 * math.pi + t2, t2)], dim=-1)

@@ -94,9 +94,12 @@ def resize_nearest(img, dsize):
     """cv2.resize(..., interpolation=cv2.INTER_NEAREST): src index = floor(dst * scale) (evaluate.py:190-191)."""
     W2, H2 = int(dsize[0]), int(dsize[1])
     a = np.asarray(img)
-    ys = np.minimum((np.arange(H2) * (a.shape[0] / H2)).astype(np.int64), a.shape[0] - 1)
-    xs = np.minimum((np.arange(W2) * (a.shape[1] / W2)).astype(np.int64), a.shape[1] - 1)
-    return a[ys][:, xs]
+    return a[nearest_table(a.shape[0], H2)][:, nearest_table(a.shape[1], W2)]
+
+
+def nearest_table(n1, n2):
+    """Source indices of resize_nearest for one axis resized from ``n1`` to ``n2`` samples (int64 [n2])."""
+    return np.minimum((np.arange(n2) * (n1 / n2)).astype(np.int64), n1 - 1)
 
 
 def preprocess_frame(img, op_shape, align_width=True):

@@ -75,13 +75,14 @@ def calc_acc(args, testloader, model, edge_model, device):
         model.raise_on_loss_flags(flags)           # two absent classes: loss.py:132 raises in the reference
         img, labels, spatialWeights, distMap, pupil_center, iris_center, elNorm, cond, imInfo = batch
         predict = mask.cpu().numpy()
-        cnp = cond.numpy().astype(np.float32)
-        iou, _, _ = getSeg_metrics(labels.numpy(), predict, cnp[:, 1])
+        cnp = cond.cpu().numpy().astype(np.float32)
+        iou, _, _ = getSeg_metrics(labels.cpu().numpy(), predict, cnp[:, 1])
         H, W = labels.shape[1:]
-        lat_p, _ = getPoint_metric(pupil_center.numpy(), elOut[:, 5:7].cpu().numpy(), cnp[:, 0], (H, W), True)
-        seg_p, _ = getPoint_metric(pupil_center.numpy(), elPred[:, 5:7].cpu().numpy(), cnp[:, 0], (H, W), True)
-        lat_i, _ = getPoint_metric(iris_center.numpy(), elOut[:, 0:2].cpu().numpy(), cnp[:, 1], (H, W), True)
-        seg_i, _ = getPoint_metric(iris_center.numpy(), elPred[:, 0:2].cpu().numpy(), cnp[:, 1], (H, W), True)
+        pupil_c, iris_c = pupil_center.cpu().numpy(), iris_center.cpu().numpy()       # (device tensors under --device_loader 1)
+        lat_p, _ = getPoint_metric(pupil_c, elOut[:, 5:7].cpu().numpy(), cnp[:, 0], (H, W), True)
+        seg_p, _ = getPoint_metric(pupil_c, elPred[:, 5:7].cpu().numpy(), cnp[:, 0], (H, W), True)
+        lat_i, _ = getPoint_metric(iris_c, elOut[:, 0:2].cpu().numpy(), cnp[:, 1], (H, W), True)
+        seg_i, _ = getPoint_metric(iris_c, elPred[:, 0:2].cpu().numpy(), cnp[:, 1], (H, W), True)
         ious.append(iou)
         dists_pupil_latent.append(lat_p); dists_pupil_seg.append(seg_p)
         dists_iris_latent.append(lat_i); dists_iris_seg.append(seg_i)
@@ -90,6 +91,9 @@ def calc_acc(args, testloader, model, edge_model, device):
     for bt, batch in enumerate(testloader):
         if args.test_normal and bt > 20:       # test.py:76
             break
+        if args.device_loader:                 # a RawBatch: the nine tensors are built on the GPU (egne_amd.loader), no augmentation
+            from egne_amd import loader
+            batch = loader.device_batch(batch, augment=False)
         waiting.append(batch)
         r = pipe.submit(batch[0].to(device), second(batch))
         if r is not None:
@@ -119,20 +123,28 @@ def main(argv=None):
     local = int(os.environ.get("LOCAL_RANK", "0"))
     torch.cuda.set_device(local)
     device = torch.device("cuda", local)
+    collate = None
+    if args.device_loader:
+        from egne_amd import loader
+        collate = loader.collate_raw
     if args.synthetic:
-        testObj = _entry.SyntheticEyes(args.synthetic)
+        testObj = loader.SyntheticRawEyes(args.synthetic) if args.device_loader else _entry.SyntheticEyes(args.synthetic)
         edge_net, model = _entry.seeded_networks(setting, args.model)
     else:
         from egne_amd.bdcn_new import BDCN
         from egne_amd.modelSummary import get_model
-        with open(os.path.join(args.path2data, 'baseline', 'cond_' + args.curObj + '.pkl'), 'rb') as f:
-            _, _, testObj = pickle.load(f)                     # test.py:271-274
+        if args.device_loader:
+            testObj = loader.RawArchive(args.raw_archive)
+        else:
+            with open(os.path.join(args.path2data, 'baseline', 'cond_' + args.curObj + '.pkl'), 'rb') as f:
+                _, _, testObj = pickle.load(f)                     # test.py:271-274
         edge_net = BDCN()
         edge_net.load_state_dict(torch.load('gen_00000016.pt', map_location='cpu')['a'])   # test.py:280-283
         model = get_model(args.model, setting)
         model.load_state_dict(torch.load(args.loadfile, map_location='cpu')['state_dict'], strict=False)
     _, samp = parallel.samplers(testObj, testObj, rank, world)
-    loader = DataLoader(testObj, batch_size=args.batchsize, shuffle=False, sampler=samp, num_workers=args.workers, drop_last=True)
+    loader = DataLoader(testObj, batch_size=args.batchsize, shuffle=False, sampler=samp, num_workers=args.workers, drop_last=True,
+                        collate_fn=collate)
     edge_net, model = edge_net.to(device).eval(), model.to(device).to(args.prec)
     return calc_acc(args, loader, model, edge_net, device)
 

@@ -52,6 +52,9 @@ def lossandaccuracy(args, loader, model, edge_model, alpha, device):
         for bt, batch in enumerate(loader):
             if args.test_normal and bt > 20:
                 break
+            if args.device_loader:      # a RawBatch (egne_amd.loader): no augmentation for validation
+                from egne_amd import loader
+                batch = loader.device_batch(batch, augment=False)
             img, labels, sw, dm, pc, ic, eln, cond, imInfo = batch
             for attempt in (0, 1, 2):
                 with torch.no_grad():
@@ -75,7 +78,7 @@ def lossandaccuracy(args, loader, model, edge_model, alpha, device):
             model.raise_on_loss_flags(model.loss_flags())       # two absent classes: loss.py:132 raises in the reference
             lsum += out[3].mean().item() * n
             nsamp += n
-            iou = getSeg_metrics(labels.numpy(), model.predictions().cpu().numpy(), cond.numpy().astype(np.float32)[:, 1])[0]
+            iou = getSeg_metrics(labels.cpu().numpy(), model.predictions().cpu().numpy(), cond.cpu().numpy().astype(np.float32)[:, 1])[0]
             if iou == iou:
                 isum += float(iou) * n
                 icnt += n
@@ -97,15 +100,24 @@ def main(argv=None):
     torch.manual_seed(0)                                      # train.py:34-36
     setting = _entry.load_setting(args.setting)
     startEp = 0
+    collate = None
+    if args.device_loader:
+        # raw samples from the Dataset, the item path of CurriculumLib.py:94-166 per batch on the GPU (egne_amd.loader.device_batch)
+        from egne_amd import loader
+        collate = loader.collate_raw
     if args.synthetic:
-        trainObj = _entry.SyntheticEyes(args.synthetic, seed=1234)   # same set on every rank; the sampler below shards it
-        validObj = _entry.SyntheticEyes(max(args.batchsize, 4), seed=99)
+        Eyes = loader.SyntheticRawEyes if args.device_loader else _entry.SyntheticEyes
+        trainObj = Eyes(args.synthetic, seed=1234)   # same set on every rank; the sampler below shards it
+        validObj = Eyes(max(args.batchsize, 4), seed=99)
         edge_net, model = _entry.seeded_networks(setting, args.model, bool(args.disentangle))
     else:
         from egne_amd.bdcn_new import BDCN
         from egne_amd.modelSummary import get_model
-        with open(os.path.join(args.path2data, 'baseline', 'cond_' + args.curObj + '.pkl'), 'rb') as f:
-            trainObj, validObj, _ = pickle.load(f)            # train.py:86-92
+        if args.device_loader:
+            trainObj, validObj = loader.split_archive(args.raw_archive)
+        else:
+            with open(os.path.join(args.path2data, 'baseline', 'cond_' + args.curObj + '.pkl'), 'rb') as f:
+                trainObj, validObj, _ = pickle.load(f)            # train.py:86-92
         edge_net = BDCN()
         edge_net.load_state_dict(torch.load('gen_00000016.pt', map_location='cpu')['a'])   # train.py:124-129
         model = get_model(args.model, setting)
@@ -139,10 +151,10 @@ def main(argv=None):
     # ITS disjoint shard of one shared per-epoch permutation, so the global batch is world * batchsize
     tsamp, vsamp = parallel.samplers(trainObj, validObj, rank, world)
     trainloader = DataLoader(trainObj, batch_size=args.batchsize, shuffle=tsamp is None, sampler=tsamp, num_workers=args.workers,
-                             drop_last=True)
+                             drop_last=True, collate_fn=collate)
     # validation keeps its partial last batch (nothing is dropped, parallel.samplers); one process: as train.py:110-121
     validloader = DataLoader(validObj, batch_size=args.batchsize, shuffle=False, sampler=vsamp, num_workers=args.workers,
-                             drop_last=vsamp is None and len(validObj) >= args.batchsize)
+                             drop_last=vsamp is None and len(validObj) >= args.batchsize, collate_fn=collate)
     # one 4-byte read of the edge plan's sticky overflow word per step, where the step's stream has the edge map (EGNE_TRAIN_OVF_CHECK=0: off)
     check_edge = os.environ.get("EGNE_TRAIN_OVF_CHECK", "1") != "0" and hasattr(edge_net, "overflowed")
     redo_edge = [False]
@@ -159,6 +171,8 @@ def main(argv=None):
         for bt, batch in enumerate(trainloader):
             if (args.overfit and bt >= args.overfit) or (args.test_normal and bt > 20):
                 break
+            if args.device_loader:      # a RawBatch: the nine tensors are built on the GPU, augmented as CurriculumLib.py:114 does for training
+                batch = loader.device_batch(batch, augment=True, on_cv2="device")
             img, labels, sw, dm, pc, ic, eln, cond, imInfo = batch
 
             def rest(edge, img=img, labels=labels, sw=sw, dm=dm, pc=pc, eln=eln, cond=cond, imInfo=imInfo):

@@ -783,6 +783,25 @@ int egne_augment(const uint8_t* img, const int64_t* label, const int32_t* choice
 int egne_augment_cv(const uint8_t* img, const int64_t* label, const int32_t* frame, const int32_t* frame_host, const double* segs,
                     const double* rot, const int32_t* q8, const double* phase, uint8_t* out_img, int64_t* out_label, int B, int H,
                     int W, void* stream);
+/* Device-side training loader (csrc/loader.hip; egne_amd.loader.device_batch): the stages of the reference's item path
+ * (CurriculumLib.py:94-166) in front of and behind the augmentation, for a batch of raw frames.
+ * egne_loader_stage: pad2Size (helperfunctions.py:406-428) and, with tap tables, scaleFn (CurriculumLib.py:78-89).  img uint8 and
+ *   label int8 [B,Rmax,Cmax]: frame b holds src_hw[b] = (rows, columns) valid pixels (int32 [B,2], device), the rest is ignored.
+ *   Every frame is centred in the H x W canvas ((H - rows) / 2 zero rows above, (W - columns) / 2 zero columns left); the caller
+ *   refuses odd or negative differences as the reference asserts (whatever src_hw holds, nothing outside a frame's valid pixels,
+ *   clamped to the buffer, is read).  Without tables Hs = H, Ws = W and the canvas is the output.  With them the image is the 8-tap
+ *   Lanczos resampling of the CANVAS to Hs x Ws: row_idx / row_w [Hs][8], col_idx / col_w [Ws][8] as for egne_eval_prep
+ *   (evaluate.lanczos4_table; a NULL pair skips that pass), the same device code, byte-identical to evaluate.resize_lanczos4 (whose
+ *   parity with OpenCV is unpinned); the label is canvas[near_row[y]][near_col[x]] (int32 [Hs], [Ws]: evaluate.resize_nearest's
+ *   indices).  out_img uint8, out_label int64 [B,Hs,Ws]: what egne_augment takes.  One launch.
+ * egne_loader_finish: after the augmentation.  out_label = label with 1 -> 0, 2 -> 1, 3 -> 2 and every other value (-1 too) kept
+ *   (CurriculumLib.py:123-125); out_img float32 [B,n] = the z-score of the uint8 image with egne_zscore's float64 statistics and
+ *   order of additions, bit-identical to egne_zscore on the float of the same pixels (a constant image: whatever 0 / 0 gives
+ *   there).  n = H*W pixels per frame.  One launch: one workgroup per frame for the z-score next to the remap's. */
+int egne_loader_stage(const uint8_t* img, const int8_t* label, const int32_t* src_hw, int B, int Rmax, int Cmax, int H, int W,
+                      int Hs, int Ws, const int32_t* row_idx, const double* row_w, const int32_t* col_idx, const double* col_w,
+                      const int32_t* near_row, const int32_t* near_col, uint8_t* out_img, int64_t* out_label, void* stream);
+int egne_loader_finish(const uint8_t* img, const int64_t* label, float* out_img, int64_t* out_label, int B, int n, void* stream);
 
 /* Device-side front and back end of evaluate.py (--device_io 1; csrc/evalio.hip), pinned bit for bit against the host functions there.
  * egne_eval_prep: preprocess_frame(grey, (Ho, Wo), align_width=True) for every eye of a batch of video frames.  src uint8 [N,Hs,Ws];
