@@ -36,8 +36,10 @@ Template builds the rows reach, per kernel file:
   msblock_dil_f16.hip    the three-product one-launch group on a map smaller than its reach and on several tiles.  Not reached: score
                          fusion, split-pair input, the plain-f16 ring form (msblock_dil1_f16.hip) -- all tested in test_gpu_ops.py.
   conv3x3_c4_f16.hip     3 -> 64 and 1 -> 40 with a post affine.  Not reached: planar input, f16 output.
-Out of scope altogether: the pair-fused launches (conv_fused_1x1_3x3_f16.hip, the convBlock head, the 1x1 with folded pooling), builds
-behind EGNE_* opt-in switches and debug builds.
+The pair-fused launches (conv_fused_1x1_3x3_f16.hip: the 1x1 + 3x3 pairs, the up-sampled addend, the convBlock head) have a sweep of
+their own, tests/test_gpu_fused_pair_sweep.py.  Out of scope here: the 1x1 with folded pooling (conv1x1_pool_f16x3_kernel: its six builds
+are value-checked against float64 by test_transition_down_pool_folded_into_the_1x1 and test_gpu_esf_encoder_tiles.py), builds behind
+EGNE_* opt-in switches and debug builds.
 
 Measured on MI355X: all 129 exact runs (43 rows x integer, fine inputs, fine weights) bit-equal on the first run, and every plan repeats its
 bits -- which is also the measurement that the f16 MFMAs keep a sum of exact products exact, as the bf16 ones do
