@@ -204,6 +204,8 @@ SIGNATURES = {
     "egne_ellipse_init_from_pred": (i32, [vp, i32, i32, i32, vp, vp, vp, vp]),
     "egne_mask_seed_workspace_bytes": (i64, [i32, i32, i32]),
     "egne_ellipse_init_from_mask": (i32, [vp, i32, vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp]),
+    "egne_class_map_cleanup_workspace_bytes": (i64, [i32, i32, i32]),
+    "egne_class_map_cleanup": (i32, [vp, i32, vp, vp, vp, vp, i32, i32, i32, i32, i32, i64, vp, vp, vp, vp, vp]),
     "egne_ellipse_iou_counts": (i32, [vp, i32, vp, vp, i32, i32, i32, vp, vp, vp, vp, i32, vp]),
     "egne_ellipse_ransac_workspace_bytes": (i64, [i32, i32, i32, i32]),
     "egne_ellipse_ransac_from_mask": (i32, [vp, i32, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, C.c_double, i32, vp, C.c_uint32, i32, vp, vp,

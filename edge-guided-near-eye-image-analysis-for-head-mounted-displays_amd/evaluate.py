@@ -12,6 +12,7 @@ videos/example1.avi) are decoded with PIL, results go to <video>_ellipses.npy in
     python evaluate.py --path2data videos --device_io 1 --device_jpeg 1 --device_decode 1     (and the input's Motion-JPEG decoding)
     python evaluate.py --path2data videos --ellipse_seed mask     (ellipse seeds from the class map instead of the regression head)
     python evaluate.py --path2data videos --ellipse_seed ransac   (seeds from the reference's ElliFit + RANSAC on the class map's boundaries)
+    python evaluate.py --path2data videos --clean_mask 1          (the class map cleaned on the device before anything reads it)
 """
 import argparse
 import glob
@@ -47,6 +48,7 @@ def parse_args(argv=None):
     p.add_argument('--device_jpeg', type=int, default=0, choices=(0, 1))  # 1: frame number and JPEG encoding on the device too (csrc/jpeg.hip); needs --device_io 1
     p.add_argument('--device_decode', type=int, default=0, choices=(0, 1))  # 1: the input's JPEG decoding on the device (csrc/jpeg_decode.hip); needs --device_io 1
     p.add_argument('--ellipse_seed', type=str, default='pred', choices=('pred', 'mask', 'ransac'))   # mask: the searches are seeded from the class map (csrc/mask_seed.hip); ransac: from ElliFit + RANSAC on its boundaries (csrc/ellifit.hip)
+    p.add_argument('--clean_mask', type=int, default=0, choices=(0, 1))   # 1: the class map is cleaned on the device before anything reads it (csrc/cleanup.hip): 3x3 opening, largest blob, holes filled
     a = p.parse_args(argv)
     if a.device_jpeg and not a.device_io:
         p.error('--device_jpeg 1 encodes the frames that --device_io 1 renders on the device: it needs --device_io 1')
@@ -134,6 +136,19 @@ RANSAC_REGIONS = {'ritnet_v2': None,                        # utils.DEFAULT_RANS
                   'deepvog': ((0, 1), (0b010, 1, 0))}
 
 
+CLEAN_LAYERS = {'ritnet_v2': None,                         # utils.DEFAULT_CLEAN_LAYERS: the iris blob of classes 1 | 2, the pupil blob painted over it
+                'deepvog': ((0b010, 1, 3),)}               # class map {0, 1 = pupil}: the pupil blob alone
+
+
+def clean_of(args):
+    """The ``clean`` keyword of _seg_and_fit for --clean_mask / --model: None (the raw argmax, as ever) or the layers of
+    utils.clean_class_maps."""
+    if args is None or not getattr(args, 'clean_mask', 0):
+        return None
+    from egne_amd.utils import DEFAULT_CLEAN_LAYERS
+    return CLEAN_LAYERS.get(getattr(args, 'model', 'ritnet_v2')) or DEFAULT_CLEAN_LAYERS
+
+
 def seed_of(args):
     """(seed, regions) of --ellipse_seed / --model: ('pred', None) unless the flag asks for the class map (mask: second moments of the
     largest component; ransac: ElliFit + RANSAC on the region's boundary, generated draws with seed 0 -- the same for every call)."""
@@ -169,7 +184,7 @@ def evaluate_ellseg_on_image(frames, model, edge_model, args=None):
         # own calibration pass)
         if _overflowed(edge_model):
             continue
-        res = _to_host(_seg_and_fit(frames, model, seed=seed, regions=regions)(edge))
+        res = _to_host(_seg_and_fit(frames, model, seed=seed, regions=regions, clean=clean_of(args))(edge))
         if not _overflowed(model):
             return res
     raise RuntimeError("non-finite activations after re-calibration: the input frames themselves are not finite")
@@ -179,12 +194,14 @@ def _overflowed(net):
     return bool(net.overflowed()) if hasattr(net, "overflowed") else False
 
 
-def _seg_and_fit(frames, model, wfit=None, then=None, seed='pred', regions=None):
+def _seg_and_fit(frames, model, wfit=None, then=None, seed='pred', regions=None, clean=None):
     """Second stage of a batch (evaluate.py:117-166): ESF-Net on the frames and their edge maps, argmax mask, both ellipses
     fitted on the device.  Returns a callable of the edge maps (egne_amd.pipeline.TwoStagePipeline runs it on its second stream).
     ``wfit`` (egne_amd.pipeline.WindowedFit): the searches go to its stream and are released in the next batch's launch window; the
     third result is then a handle (``_to_host`` waits for it); ``then(edge, mask, fit)`` is queued on the searches' stream right behind
-    them (the device-side rendering of --device_io 1).  ``seed`` / ``regions``: seed_of(args)."""
+    them (the device-side rendering of --device_io 1).  ``seed`` / ``regions``: seed_of(args).  ``clean`` (clean_of(args)): layers
+    of utils.clean_class_maps -- the class map is cleaned right behind model.predictions(), on the same stream, and seeds, search,
+    renderers and the returned map all read the cleaned tensor (a fresh one per call: it lives as long as whoever holds it)."""
     dev = frames.device
     N, _, H, W = frames.shape
 
@@ -196,6 +213,14 @@ def _seg_and_fit(frames, model, wfit=None, then=None, seed='pred', regions=None)
             z = lambda *s: torch.zeros(s, device=dev)              # noqa: E731
             out = model(frames, edge, labels.long(), z(N, 2), z(N, 2, 5), z(N, H, W), z(N, 3, H, W), z(N, 4),
                         torch.zeros(N, dtype=torch.long, device=dev), 0)
+            if clean is not None:
+                from egne_amd.utils import clean_class_maps
+                m = clean_class_maps(model.predictions(), clean)          # (the closure of WindowedFit.submit keeps it until its searches ran)
+                if wfit is not None:
+                    e = edge[:, 0].clone()
+                    return e, m, wfit.submit(m, out[1], then=None if then is None else (lambda fit: then(e, m, fit)),
+                                             seed=seed, regions=regions)
+                return edge[:, 0].clone(), m, _fit(m, out[1], seed, regions)
             if wfit is not None:
                 e, m = edge[:, 0].clone(), model.predictions().clone()
                 return e, m, wfit.submit(model.predictions(), out[1], then=None if then is None else (lambda fit: then(e, m, fit)),
@@ -205,7 +230,7 @@ def _seg_and_fit(frames, model, wfit=None, then=None, seed='pred', regions=None)
     return run
 
 
-def graphed_runner(warmup_frames, model, edge_model, seed='pred', regions=None):
+def graphed_runner(warmup_frames, model, edge_model, seed='pred', regions=None, clean=None):
     """edge -> seg -> fit of a fixed small batch as one hipGraph replay (egne_amd.pipeline.GraphedFrames): the per-eye loop of
     evaluate.py:235-249 at one or two frames per call.  ``runner(frames)`` returns the same device tensors as the eager path (edge maps
     [N,H,W], class maps [N,H,W], fitted ellipses [N,2,5]); results are bit-identical to it."""
@@ -214,11 +239,11 @@ def graphed_runner(warmup_frames, model, edge_model, seed='pred', regions=None):
     ns = argparse.Namespace(prec=torch.float32, edge_thres=0)
 
     def stage(x):
-        return _seg_and_fit(x, model, seed=seed, regions=regions)(calc_edge(ns, x, edge_model, x.device))
+        return _seg_and_fit(x, model, seed=seed, regions=regions, clean=clean)(calc_edge(ns, x, edge_model, x.device))
     return GraphedFrames(stage, warmup_frames)
 
 
-def graphed_runner_io(warmup_u8, model, edge_model, op_shape=(240, 320), eyes=2, eye_width=320, seed='pred', regions=None):
+def graphed_runner_io(warmup_u8, model, edge_model, op_shape=(240, 320), eyes=2, eye_width=320, seed='pred', regions=None, clean=None):
     """graphed_runner with the device front and back end INSIDE the captured graph: uint8 frames [N,Hs,Ws] in, (overlay, edge frame,
     ellipses at source geometry) out -- prep, edge, seg, fit and rendering are one replay.  Capture allows it: shapes are fixed, the
     tap tables are uploaded by the eager warm-up runs, nothing in the two stages synchronises."""
@@ -228,12 +253,13 @@ def graphed_runner_io(warmup_u8, model, edge_model, op_shape=(240, 320), eyes=2,
 
     def stage(fu):
         x, ss = preprocess_frames_device(fu, op_shape, eyes, eye_width)
-        edge, seg, fit = _seg_and_fit(x, model, seed=seed, regions=regions)(calc_edge(ns, x, edge_model, x.device))
+        edge, seg, fit = _seg_and_fit(x, model, seed=seed, regions=regions, clean=clean)(calc_edge(ns, x, edge_model, x.device))
         return render_frames_device(fu, edge, seg, fit, ss, eyes, eye_width)
     return GraphedFrames(stage, warmup_u8)
 
 
-def evaluate_frames_device_io(frames_u8, model, edge_model, op_shape=(240, 320), eyes=2, eye_width=320, seed='pred', regions=None):
+def evaluate_frames_device_io(frames_u8, model, edge_model, op_shape=(240, 320), eyes=2, eye_width=320, seed='pred', regions=None,
+                              clean=None):
     """evaluate_ellseg_on_image from uint8 device frames to rendered device frames (eager; the redo path of --device_io 1): the same
     re-calibration retries, nothing crosses to the host but the plans' overflow words."""
     from egne_amd.utils import calc_edge
@@ -244,7 +270,7 @@ def evaluate_frames_device_io(frames_u8, model, edge_model, op_shape=(240, 320),
             edge = calc_edge(ns, x, edge_model, x.device)
         if _overflowed(edge_model):
             continue
-        e, m, fit = _seg_and_fit(x, model, seed=seed, regions=regions)(edge)
+        e, m, fit = _seg_and_fit(x, model, seed=seed, regions=regions, clean=clean)(edge)
         if not _overflowed(model):
             return render_frames_device(frames_u8, e, m, fit, ss, eyes, eye_width)
     raise RuntimeError("non-finite activations after re-calibration: the input frames themselves are not finite")
@@ -930,6 +956,7 @@ def evaluate_ellseg_per_video(path_vid, args, model, edge_model, device):
         sys.exit('evaluate.py: --device_decode 1 needs --device_io 1')
     runner = [None]
     seed, regions = seed_of(args)                   # --ellipse_seed mask: every path below seeds the searches from the class map
+    clean = clean_of(args)                          # --clean_mask 1: every path below reads the cleaned class map
 
     def flush():
         if not pending:
@@ -942,11 +969,11 @@ def evaluate_ellseg_per_video(path_vid, args, model, edge_model, device):
             # one hipGraph replay per frame pair (egne_amd.pipeline.GraphedFrames, captured on the first frame): no batching, no
             # pipelining across frames -- 4.3-4.7 ms per call on MI355X instead of a batch of 32 every ~20 ms
             if runner[0] is None or tuple(runner[0].x.shape) != tuple(x.shape):
-                runner[0] = graphed_runner(x, model, edge_model, seed, regions)
+                runner[0] = graphed_runner(x, model, edge_model, seed, regions, clean)
             res = [t.clone() for t in runner[0](x)]
             if _overflowed(model) | _overflowed(edge_model):
                 # beyond the head-room of the scales baked into the captured launches: capture again (its eager warm-up runs re-calibrate)
-                runner[0] = graphed_runner(x, model, edge_model, seed, regions)
+                runner[0] = graphed_runner(x, model, edge_model, seed, regions, clean)
                 res = [t.clone() for t in runner[0](x)]
                 if _overflowed(model) | _overflowed(edge_model):
                     raise RuntimeError("non-finite activations after re-calibration: the input frames themselves are not finite")
@@ -958,7 +985,7 @@ def evaluate_ellseg_per_video(path_vid, args, model, edge_model, device):
             return
         queued.append(list(pending))
         pending.clear()
-        r = pipe.submit(x, _seg_and_fit(x, model, wfit, seed=seed, regions=regions))
+        r = pipe.submit(x, _seg_and_fit(x, model, wfit, seed=seed, regions=regions, clean=clean))
         if r is not None:
             ready.append((queued.pop(0), r))
         while len(ready) > 1:
@@ -995,12 +1022,12 @@ def evaluate_ellseg_per_video(path_vid, args, model, edge_model, device):
             if runner[0] is None or tuple(runner[0].x.shape) != tuple(batch.fu.shape):
                 if dd:
                     fix_flagged(batch)
-                runner[0] = graphed_runner_io(batch.fu, model, edge_model, (240, 320), 2, ew, seed, regions)
+                runner[0] = graphed_runner_io(batch.fu, model, edge_model, (240, 320), 2, ew, seed, regions, clean)
             res = runner[0](batch.fu)
             if _overflowed(model) | _overflowed(edge_model):
                 if dd:
                     fix_flagged(batch)
-                runner[0] = graphed_runner_io(batch.fu, model, edge_model, (240, 320), 2, ew, seed, regions)
+                runner[0] = graphed_runner_io(batch.fu, model, edge_model, (240, 320), 2, ew, seed, regions, clean)
                 res = runner[0](batch.fu)
                 if _overflowed(model) | _overflowed(edge_model):
                     raise RuntimeError("non-finite activations after re-calibration: the input frames themselves are not finite")
@@ -1018,7 +1045,7 @@ def evaluate_ellseg_per_video(path_vid, args, model, edge_model, device):
             if dj:
                 _encode_rendered(batch)
         queued.append(batch)
-        r = pipe.submit(x, _seg_and_fit(x, model, wfit, then, seed, regions))
+        r = pipe.submit(x, _seg_and_fit(x, model, wfit, then, seed, regions, clean))
         if r is not None:
             ready.append((queued.pop(0), r))
         while len(ready) > 1:
@@ -1039,7 +1066,7 @@ def evaluate_ellseg_per_video(path_vid, args, model, edge_model, device):
         if again:
             # as draw(): this batch and the one queued behind it again, from the retained uint8 device frames, rendered again
             torch.cuda.synchronize()
-            batch.rendered = evaluate_frames_device_io(batch.fu, model, edge_model, (240, 320), 2, ew, seed, regions)
+            batch.rendered = evaluate_frames_device_io(batch.fu, model, edge_model, (240, 320), 2, ew, seed, regions, clean)
             if dj:
                 _encode_rendered(batch)
         if dj:

@@ -341,6 +341,81 @@ def _seeds_from_mask_rows(L, m, fo_in, cb, sc, min_area, return_stats):
     return (init, fo, cl, stats, status) if return_stats else (init, fo, cl)
 
 
+DEFAULT_CLEAN_LAYERS = ((0b110, 1, 3), (0b100, 2, 3))     # the iris blob of classes 1 | 2 (largest, holes filled), then the pupil blob over it
+_layer_cache = {}
+
+
+def _layer_rows(layers, F, dev):
+    """frame_of / class_bits / paint_cls / flags [L*F] int32 on the device for ``layers`` repeated over F frames (row L*f + j), cached
+    like the seeds' tables: the upload happens on the first (eager) call, so a captured graph only reads them."""
+    try:
+        layers = tuple(tuple(int(v) for v in r) for r in layers)
+    except (TypeError, ValueError):
+        raise ValueError("layers: (class_bits, paint_cls, flags) triples, got %r" % (layers,))
+    if not layers:
+        raise ValueError("layers: at least one (class_bits, paint_cls, flags) triple")
+    for r in layers:
+        if len(r) != 3:
+            raise ValueError("layers: (class_bits, paint_cls, flags) triples, got %r" % (r,))
+        if not 0 <= r[0] < 1 << 32:
+            raise ValueError("layers: class_bits %r is not a bitmask over class ids 0..31" % (r[0],))
+        if not -(1 << 31) <= r[1] < 1 << 31:
+            raise ValueError("layers: paint_cls %r does not fit 32 bits" % (r[1],))
+        if not 0 <= r[2] <= 3:
+            raise ValueError("layers: flags %r (bit 0: largest component, bit 1: fill its holes)" % (r[2],))
+    key = (layers, int(F), str(dev))
+    if key not in _layer_cache:
+        fo = np.repeat(np.arange(F, dtype=np.int32), len(layers))
+        cb = np.tile(np.array([r[0] for r in layers], dtype=np.uint32).view(np.int32), F)
+        pc = np.tile(np.array([r[1] for r in layers], dtype=np.int32), F)
+        fl = np.tile(np.array([r[2] for r in layers], dtype=np.int32), F)
+        _layer_cache[key] = tuple(torch.from_numpy(a).to(dev) for a in (fo, cb, pc, fl))
+    return _layer_cache[key]
+
+
+def clean_class_maps(mask, layers=DEFAULT_CLEAN_LAYERS, open3=True, min_area=1, fill_cls=0, out=None, return_stats=False):
+    """Cleaned class maps (csrc/cleanup.hip; the contract is in include/egne_hip.h): per-class 3x3 opening (the
+    reference's helperfunctions.clean_mask), then per layer the largest 8-connected blob with its holes filled, painted in layer order
+    over ``fill_cls``.
+
+    mask [F,H,W] int64 class maps on the GPU; ``layers`` lists (class_bits, paint_cls, flags) applied to every frame: a pixel belongs
+    to the layer iff it survives the opening of its own class (``open3``; every id 0..31 survives without it) and bit mask[p] of
+    class_bits is set; flags bit 0 keeps the largest component only, bit 1 fills the holes of what is kept; a layer with fewer than
+    ``min_area`` pixels left paints nothing.  Returns the cleaned maps, int64 [F,H,W] on the device (``out`` if given: contiguous,
+    same shape, not overlapping ``mask``).  With ``return_stats`` also stats int64 [L*F,4] = (pixels of the layer, its components,
+    pixels kept, pixels added by filling; row L*f + j is layer j of frame f) and the int32 status word (0 = every loop ended inside
+    its bound).  Nothing here synchronises."""
+    require_cuda(mask, "mask")
+    if mask.dtype != torch.int64 or mask.dim() != 3:
+        raise ValueError("mask must be an int64 [F,H,W] tensor")
+    L = _lib.lib()
+    dev = mask.device
+    F, H, W = (int(v) for v in mask.shape)
+    min_area = int(min_area)
+    if min_area < 1:
+        raise ValueError("clean_class_maps: min_area %d (at least 1)" % min_area)
+    fo, cb, pc, fl = _layer_rows(DEFAULT_CLEAN_LAYERS if layers is None else layers, F, dev)
+    n = int(fo.shape[0])
+    nbytes = int(L.egne_class_map_cleanup_workspace_bytes(n, H, W))
+    if nbytes < 0:
+        raise ValueError("clean_class_maps: %d rows of %dx%d class maps (2..1024 rows and columns, at most 2^20 pixels)" % (n, H, W))
+    m = mask.contiguous()
+    if out is None:
+        out = torch.empty((F, H, W), dtype=torch.int64, device=dev)
+    elif out.dtype != torch.int64 or tuple(out.shape) != (F, H, W) or not out.is_contiguous() or out.device != dev:
+        raise ValueError("out must be a contiguous int64 [%d,%d,%d] tensor on the device of mask" % (F, H, W))
+    span = F * H * W * 8
+    if F and m.data_ptr() < out.data_ptr() + span and out.data_ptr() < m.data_ptr() + span:
+        raise ValueError("clean_class_maps: out overlaps mask")
+    ws = torch.empty((nbytes + 7) // 8, dtype=torch.int64, device=dev)
+    stats = torch.empty((n, 4), dtype=torch.int64, device=dev)
+    status = torch.empty((1,), dtype=torch.int32, device=dev)
+    _lib.check(L.egne_class_map_cleanup(m.data_ptr(), F, fo.data_ptr(), cb.data_ptr(), pc.data_ptr(), fl.data_ptr(), n, H, W,
+                                        1 if open3 else 0, min_area, int(fill_cls), out.data_ptr(), stats.data_ptr(), status.data_ptr(),
+                                        ws.data_ptr(), _lib.stream_ptr()), "class_map_cleanup")
+    return (out, stats, status) if return_stats else out
+
+
 DEFAULT_RANSAC_REGIONS = ((0b110, 1, 0), (0b100, 2, 0b001))     # iris: boundary of classes 1 and 2 together; pupil: class 2 without
                                                                 # background-adjacent points (getValidPoints' condPupil)
 DEEPVOG_RANSAC_REGIONS = ((0, 1), (0b010, 1, 0))

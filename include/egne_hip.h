@@ -710,6 +710,35 @@ int egne_ellipse_init_from_mask(const int64_t* mask, int nframes, const int32_t*
                                 void* stream);
 
 /*
+ * Class-map clean-up (evaluate.py --clean_mask 1; csrc/cleanup.hip): which pixels count, decided before any ellipse is
+ * fitted.  The first step restates the reference's helperfunctions.clean_mask (:378-392, called by none of its scripts); keeping the
+ * largest blob and filling its holes is not in the reference.  Integer-exact.
+ * mask [nframes][H][W] int64 class ids; row i < n = (frame_of[i], class_bits[i], paint_cls[i], flags[i]); open3 0 or 1; min_area >= 1.
+ * Step 1, opening (open3 = 1), per class id c in 0..31 that a row names: S_c = {p : mask[p] == c}; E_c = the pixels of S_c whose
+ * 4-neighbours inside the frame are all in S_c (neighbours outside the frame do not constrain: cv2.erode's default border); O_c = E_c
+ * and the 4-neighbours of E_c inside the frame (cv2.dilate, border = background); O_c is a subset of S_c.  A pixel is eligible iff it
+ * lies in the O of its own class; with open3 = 0 every pixel with an id in 0..31 is.  Ids outside 0..31 are never eligible.  The
+ * element is the cross of cv2.getStructuringElement(cv2.MORPH_ELLIPSE, (3, 3)), restated from OpenCV's documented behaviour.
+ * Step 2, per row: R = the eligible pixels of frame frame_of[i] whose bit mask[p] is set in class_bits[i].  flags & 1: K = the
+ * 8-connected component of R with the most pixels (tie: the one whose first pixel comes first in raster order, the rule of
+ * egne_ellipse_init_from_mask); otherwise K = R.  Fewer than min_area pixels in K: the row paints nothing.  flags & 2: every
+ * 4-connected component of frame \ K without a pixel of the first or last row or column is added to K
+ * (scipy.ndimage.binary_fill_holes; dropped components of R inside such a hole are filled with it).
+ * Step 3: out[f] = fill_cls everywhere, then the rows of frame f paint paint_cls[i] over their K in row order.  A row whose frame_of
+ * is outside [0, nframes) paints nothing; a frame no row names is all fill_cls.  Every pixel of out is written exactly once.
+ * stats [n][4] int64 = (pixels of R, components of R, pixels of K before filling, pixels added by filling).  Every find / union loop
+ * stops after 4*H*W + 64 steps: such a row sets bit 0 of the device word `status` (zeroed by the call) and paints nothing.
+ * Refused (nothing written): H < 2, W < 2, max(H, W) > 1024, H*W > 2^20; out overlapping mask.  ws:
+ * egne_class_map_cleanup_workspace_bytes(n, H, W) bytes (-1 for a refused shape), aligned to 8: all scratch lives there.  Eleven
+ * launches on `stream`, fixed sequence (capturable), no host synchronisation; the launch boundary is the only synchronisation
+ * between workgroups.
+ */
+int64_t egne_class_map_cleanup_workspace_bytes(int n, int H, int W);
+int egne_class_map_cleanup(const int64_t* mask, int nframes, const int32_t* frame_of, const int32_t* class_bits,
+                           const int32_t* paint_cls, const int32_t* flags, int n, int H, int W, int open3, int min_area,
+                           int64_t fill_cls, int64_t* out, int64_t* stats, int32_t* status, void* ws, void* stream);
+
+/*
  * Ellipses from class-map boundaries (csrc/ellifit.hip): the reference's helperfunctions.ElliFit (:209-276) under
  * helperfunctions.ransac (:278-310), the estimator behind its dataset_generation/Extract*.py "Fits", per (frame, region) row on the
  * device -- it replaces ransac(pts, ElliFit, n_min, iters, thres, n_good).loop() and my_ellipse(model).verify(pts) on the host.
