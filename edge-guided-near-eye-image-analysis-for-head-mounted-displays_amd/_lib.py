@@ -164,6 +164,9 @@ SIGNATURES = {
     "egne_bdcn_tail": (i32, [C.POINTER(BdcnTailDesc), vp]),
     "egne_loss_workspace_floats": (i64, [i32, i32, i32]),
     "egne_loss_fwd": (i32, [C.POINTER(LossDesc), vp]),
+    "egne_selfcorr_workspace_floats": (i64, [i32, i32, i32]),
+    "egne_selfcorr_fwd": (i32, [C.POINTER(LossDesc), f32, vp, vp, vp]),
+    "egne_selfcorr_bwd": (i32, [C.POINTER(LossDesc), f32, vp, vp, vp, vp, vp, vp]),
     "egne_ellipse_head_act": (i32, [vp, i32, i32, vp]),
     "egne_selu_inplace": (i32, [vp, i64, vp]),
     "egne_spatial_mean": (i32, [vp, i64, i32, i32, i32, i32, vp, vp]),

@@ -25,7 +25,8 @@ _TRAINING = (
     ("workers", int, 0, "DataLoader worker processes"),
     ("overfit", int, 0, "N > 0: stop every epoch after N batches"),
     ("resume", int, 0, "1: continue from --loadfile"),
-    ("selfCorr", int, 0, "self-consistency loss term (off in the reference pipeline; not built here)"),
+    ("selfCorr", int, 0, "1: add 10 * the self-consistency term to the loss (loss.py:187-219: the ellipses of elPred rasterised into soft masks "
+                          "and held against the softmax; forward and backward on the device; off in the reference pipeline)"),
     ("disentangle", int, 1, "dataset-identity confusion loss on the latent"),
 )
 _MODEL = (

@@ -593,7 +593,7 @@ def build_forward_plan(model, B, H, W, dev, training, dtype=torch.float32):
         pl.raw(pl._elout_copy, (), "elOut.copy")
     else:
         regression_head(pl, model.elReg, xb, B, hb, wb, training)
-    loss_head(pl, opb, B, H, W, dev, training)
+    loss_head(pl, opb, B, H, W, dev, training, selfcorr=bool(getattr(model, "selfCorr", False)))
     confusion_head(pl, model, fc, B, training, variant == "v2")
     if training:
         bw = pl.build_backward()
@@ -651,9 +651,13 @@ def regression_head(pl, rg, xb, B, hb, wb, training):
 
 
 
-def loss_head(pl, opb, B, H, W, dev, training):
+SELFCORR_WEIGHT = 10.0      # loss += 10 * loss_selfCorr (models/RITnet_v2.py:341, RITnet_v1.py:287)
+
+
+def loss_head(pl, opb, B, H, W, dev, training, selfcorr=False):
     """get_allLoss (models/RITnet_v2.py:372-432 = models/RITnet_v1.py:322-372) on the logits buffer ``opb`` [B,H,W,8]: the loss
-    kernel's descriptor, ground-truth staging tensors, argmax mask and NCHW logits."""
+    kernel's descriptor, ground-truth staging tensors, argmax mask and NCHW logits.  ``selfcorr``: the self-consistency term of
+    ``model.selfCorr`` behind it (csrc/selfcorr.hip), ``pl.sc_terms`` = (term, n_ok, 10 * term, 0)."""
     L = pl.L
     ld = _lib.LossDesc()
     pl.t_target = pl.vec(B, H, W, dtype=torch.int64)
@@ -687,12 +691,29 @@ def loss_head(pl, opb, B, H, W, dev, training):
         ld.coef = pl.coef.data_ptr()
         pl.gscale = pl.vec(1)
     pl.raw(L.egne_loss_fwd, (C.byref(ld),), "loss")
+    pl.sc_terms = pl.up_grads = None
+    if selfcorr:
+        # 10 * get_selfConsistency(op, elPred, 1 - cond[:, 1]) (RITnet_v2.py:339-341, RITnet_v1.py:286-287; in eval() too): behind the
+        # loss kernel that writes elPred, in front of the confusion head
+        pl.sc_terms = pl.vec(4)
+        sc_ws = pl.vec(int(L.egne_selfcorr_workspace_floats(B, H, W)))
+        pl.raw(L.egne_selfcorr_fwd, (C.byref(ld), SELFCORR_WEIGHT, sc_ws.data_ptr(), pl.sc_terms.data_ptr()), "selfcorr")
     if training:
         def emit_loss(bw):
             go = pl.gbuf(opb)
             bw.raw(L.egne_loss_bwd, (C.byref(ld), pl.gscale.data_ptr(), go.data_ptr(), go.shape[-1], 0,
                                      pl.g_elOut.data_ptr()), "loss.bwd")
         pl.tape.append(emit_loss)
+        if selfcorr:
+            # the term's gradient goes through the three upstream tensors egne_loss_bwd reads (logits, soft-argmax centres, elOut): the
+            # plan owns them, zero between two passes; a caller's own upstream gradients are added into them (_ESFFunction.backward)
+            pl.up_grads = (pl.vec(B, 3, H, W), pl.vec(B, 2, 2), pl.vec(B, 10))
+            ld.g_op_nchw, ld.g_pred_c, ld.g_elOut_up = (t.data_ptr() for t in pl.up_grads)
+
+            def emit_selfcorr(bw):
+                bw.raw(L.egne_selfcorr_bwd, (C.byref(ld), SELFCORR_WEIGHT, sc_ws.data_ptr(), pl.gscale.data_ptr())
+                       + tuple(t.data_ptr() for t in pl.up_grads), "selfcorr.bwd")
+            pl.tape.append(emit_selfcorr)      # the tape is replayed in reverse: runs in front of loss.bwd
 
 
 

@@ -170,7 +170,7 @@ def build_plan(model, B, H, W, dev, training, dtype=torch.float32):
     opb = pl.buf(B, H, W, 8)
     l = E._cl(model.dec.final, E._lay([cur]), act=ACT_NONE)
     pl.conv(l, [cur], Piece(opb, 0, 3), B, H, W, name="dec.final")
-    E.loss_head(pl, opb, B, H, W, dev, training)
+    E.loss_head(pl, opb, B, H, W, dev, training, selfcorr=bool(model.selfCorr))
     E.confusion_head(pl, model, fc, B, training, True)
     if training:
         pl.build_backward()

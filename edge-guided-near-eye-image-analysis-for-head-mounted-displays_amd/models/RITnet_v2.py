@@ -119,7 +119,9 @@ class _ESFFunction(torch.autograd.Function):
         """``loss.backward()`` alone (train.py:285-286) is the fast path.  A caller that adds its own terms on ``op`` / ``elPred`` /
         ``latent`` / ``elOut`` (all four carry grad in the reference, models/RITnet_v2.py:334-354) hands their gradients in here: the
         loss head's backward kernel adds them to its own (egne_loss_desc.g_op_nchw / g_pred_c / g_elOut_up), the latent's joins the
-        bottleneck gradient in front of its spatial-mean backward.  No synchronisation either way."""
+        bottleneck gradient in front of its spatial-mean backward.  A selfCorr plan owns those three tensors (zero between two passes:
+        the term's backward launch adds its gradient to them, esf_engine.loss_head), so a caller's gradients are added into them
+        instead and they are cleared behind the run.  No synchronisation either way."""
         model, pl = ctx.model, ctx.pl
         if g_loss is None and all(g is None for g in (g_op, g_elPred, g_latent, g_elOut)):
             return None, None, None
@@ -132,30 +134,47 @@ class _ESFFunction(torch.autograd.Function):
         ld, keep = pl.loss_desc, []
         B = pl.elOut.shape[0]
         f32 = lambda t: t.detach().to(torch.float32).contiguous()  # noqa: E731
-        if g_op is not None:
-            keep.append(f32(g_op))
-            ld.g_op_nchw = keep[-1].data_ptr()
-        if g_elPred is not None or g_elOut is not None:
-            up = torch.zeros(B, 10, device=pl.elOut.device)
+        own = pl.up_grads        # selfCorr plans: the descriptor points at the plan's own (zero) upstream tensors, the term's backward adds to them
+        if own is not None:
+            if g_op is not None:
+                own[0].add_(f32(g_op))
             if g_elOut is not None:
-                up += f32(g_elOut)
+                own[2].add_(f32(g_elOut))
             if g_elPred is not None:
-                ge = f32(g_elPred)
-                up[:, 2:5] += ge[:, 2:5]
-                up[:, 7:10] += ge[:, 7:10]
-                # no mask in the batch: the iris centre of elPred is a copy of elOut[:, 5:7] (RITnet_v2.py:404), else the soft-argmax
-                # of the logits; egne_loss_bwd routes g_pred_c's iris row accordingly (out_terms[5], read on the device)
-                keep.append(torch.cat((ge[:, 0:2], ge[:, 5:7]), 1).contiguous())
-                ld.g_pred_c = keep[-1].data_ptr()
-            keep.append(up)
-            ld.g_elOut_up = up.data_ptr()
+                ge, pc = f32(g_elPred), own[1].view(B, 4)
+                own[2][:, 2:5] += ge[:, 2:5]
+                own[2][:, 7:10] += ge[:, 7:10]
+                pc[:, 0:2] += ge[:, 0:2]
+                pc[:, 2:4] += ge[:, 5:7]
+        else:
+            if g_op is not None:
+                keep.append(f32(g_op))
+                ld.g_op_nchw = keep[-1].data_ptr()
+            if g_elPred is not None or g_elOut is not None:
+                up = torch.zeros(B, 10, device=pl.elOut.device)
+                if g_elOut is not None:
+                    up += f32(g_elOut)
+                if g_elPred is not None:
+                    ge = f32(g_elPred)
+                    up[:, 2:5] += ge[:, 2:5]
+                    up[:, 7:10] += ge[:, 7:10]
+                    # no mask in the batch: the iris centre of elPred is a copy of elOut[:, 5:7] (RITnet_v2.py:404), else the soft-argmax
+                    # of the logits; egne_loss_bwd routes g_pred_c's iris row accordingly (out_terms[5], read on the device)
+                    keep.append(torch.cat((ge[:, 0:2], ge[:, 5:7]), 1).contiguous())
+                    ld.g_pred_c = keep[-1].data_ptr()
+                keep.append(up)
+                ld.g_elOut_up = up.data_ptr()
         pl._g_latent_up = f32(g_latent) if g_latent is not None else None
         gc = getattr(model, "grad_comm", None)        # parallel.overlap_grads: the early bucket of the gradient all-reduce
         pl.bw.tail_hook = gc.tail_ready if gc is not None else None
         try:
             pl.bw.run(model._events)
         finally:
-            ld.g_op_nchw = ld.g_pred_c = ld.g_elOut_up = None
+            if own is not None:
+                for t in own:
+                    t.zero_()
+            else:
+                ld.g_op_nchw = ld.g_pred_c = ld.g_elOut_up = None
             pl._g_latent_up = None
             pl.bw.tail_hook = None
         pl._upstream_keep = keep          # alive until the next backward (the launches are asynchronous)
@@ -268,7 +287,8 @@ class DenseNet2D(nn.Module):
 
     def _plan(self, B, H, W, dev):
         st = self.storage_dtype if self.training else torch.float32
-        key = (B, H, W, dev, bool(self.training), bool(self.disentangle), bool(self.toggle), st)
+        # (index 4 is the training flag: _ensure_grad_arena drops training plans by it)
+        key = (B, H, W, dev, bool(self.training), bool(self.disentangle), bool(self.toggle), st, bool(self.selfCorr))
         if key not in self._plans:
             self._plans[key] = self._build_plan(B, H, W, dev, bool(self.training), st)
         return self._plans[key]
@@ -286,8 +306,6 @@ class DenseNet2D(nn.Module):
         want_grad = torch.is_grad_enabled() and self.training and any(p.requires_grad for p in self.parameters())
         if want_grad:
             self._ensure_grad_arena()
-        if self.selfCorr:
-            raise NotImplementedError("selfCorr is disabled in the reference pipeline (--selfCorr 0, args.py:41)")
         B, _, H, W = x.shape
         pl = self._plan(B, H, W, x.device)
         self._last_plan = pl
@@ -326,6 +344,16 @@ class DenseNet2D(nn.Module):
         their scales on the device (or have none: bf16 storage) and never report."""
         last = getattr(self, "_last_plan", None)
         return last is not None and last.overflowed()
+
+    def selfcorr_term(self):
+        """Device scalar [1]: the self-consistency term of the last forward (``selfCorr`` set), before its weight of 10 -- what the
+        reference prints at every step (models/RITnet_v2.py:342).  A copy; nothing is printed and nothing synchronises."""
+        last = getattr(self, "_last_plan", None)
+        if last is None:
+            raise RuntimeError("selfcorr_term(): no forward pass has run yet")
+        if last.sc_terms is None:
+            raise RuntimeError("selfcorr_term(): the last forward ran with selfCorr off")
+        return last.sc_terms[0:1].clone()
 
     def loss_flags(self):
         """Device scalar: the number of samples of the last forward whose ground-truth mask lacks TWO classes.  The reference's

@@ -466,6 +466,27 @@ typedef struct {
 int64_t egne_loss_workspace_floats(int B, int H, int W);
 int egne_loss_fwd(const egne_loss_desc* d, void* stream);
 
+/* Self-consistency term (loss.py:187-219 get_selfConsistency; models/RITnet_v2.py:339-341, RITnet_v1.py:286-287), csrc/selfcorr.hip.
+ * With q_e(x, y) = (X/a)^2 + (Y/b)^2 in the frame of ellipse e = (cx, cy, a, b, theta) over the mesh grid_x x grid_y (both required),
+ *   t_pup = sigmoid(64 (1 - q_pupil)),  t_bg = sigmoid(64 (q_iris - 1)),  kl(t, lp) = t (log t - lp),  lp = log_softmax(logits),
+ *   term  = sum_b ok_b (mean_pix kl(t_pup, lp[2]) + mean_pix kl(t_bg, lp[0])) / n_ok,  ok_b = 1 - cond[b][1],  n_ok = sum_b ok_b,
+ * 0 when n_ok == 0.  The iris ellipse is d->elPred[b][0:5], the pupil ellipse d->elPred[b][5:10] (axes non-zero): the call runs behind
+ * egne_loss_fwd with the same descriptor and in front of egne_conf_loss.  Reads logits (either storage), cond, elPred and the mesh.
+ *   sc_terms[4] = term, n_ok, weight * term, 0;   d->out_terms[0] += weight * term (the reference's weight is 10).
+ * ws: egne_selfcorr_workspace_floats(B, H, W) floats, kept for the backward.  Two launches (per-(sample, block) partial sums, one
+ * combining block), no atomics. */
+int64_t egne_selfcorr_workspace_floats(int B, int H, int W);
+int egne_selfcorr_fwd(const egne_loss_desc* d, float weight, float* ws, float* sc_terms, void* stream);
+/* Its backward, gscale[0] * weight * d term / d ., ADDED to the three tensors egne_loss_bwd reads as upstream gradients (one launch, every
+ * element has one writer):
+ *   g_op_nchw [B,3,H,W] += w (t_pup (p_k - [k == 2]) + t_bg (p_k - [k == 0])),  w = weight * gscale * ok_b / (H W n_ok), p = softmax;
+ *   g_pred_c  [B,2,2]   += d / d (iris centre, pupil centre), the entries 0:2 and 5:7 of elPred;
+ *   g_elOut_up[B,10]    += entries 2:5 and 7:10 only (axes and angle of both ellipses), 0:2 and 5:7 are not touched.
+ * d kl / d z = t (1 - t) (log t - lp + 1) is taken as its limit 0 where t or 1 - t underflows (the reference's autograd gives NaN
+ * there): finite for finite inputs.  A sample with ok_b == 0, or a batch with n_ok == 0, adds nothing (the destinations keep their bits). */
+int egne_selfcorr_bwd(const egne_loss_desc* d, float weight, const float* ws, const float* gscale /* device, 1 float */,
+                      float* g_op_nchw, float* g_pred_c, float* g_elOut_up, void* stream);
+
 /* Loss of the DeepVOG comparator (models/deepvog_pytorch.py:148-167 get_allLoss), forward only: 10 * cross_entropy(softmax(op), label == 2)
  * averaged per frame and over the frames with cond[:,1] == 0, plus the mean L1 distance between the soft-argmax centre of channel 1
  * (loss.py:16-46, temperature 4) and utils.normPts(pupil_center).  logits: two channels of an NHWC fp32 slice.  Also writes the NCHW logits
