@@ -213,6 +213,8 @@ SIGNATURES = {
     "egne_ellipse_ransac_workspace_bytes": (i64, [i32, i32, i32, i32]),
     "egne_ellipse_ransac_from_mask": (i32, [vp, i32, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, C.c_double, i32, vp, C.c_uint32, i32, vp, vp,
                                             vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+    "egne_seg_confusion_counts": (i32, [vp, vp, i32, i32, i32, i32, vp, vp]),
+    "egne_score_rows": (i32, [vp, i32, i32, vp, vp, vp, vp, vp, vp, i32, vp, i32, i32, i32, vp, i64, i64, vp]),
     "egne_last_error": (C.c_char_p, []),
     "egne_version": (i32, []),
     "egne_sizeof": (i32, [i32]),

@@ -28,6 +28,10 @@ _TRAINING = (
     ("selfCorr", int, 0, "1: add 10 * the self-consistency term to the loss (loss.py:187-219: the ellipses of elPred rasterised into soft masks "
                           "and held against the softmax; forward and backward on the device; off in the reference pipeline)"),
     ("disentangle", int, 1, "dataset-identity confusion loss on the latent"),
+    ("track_scores", int, 0, "1: the per-batch scores of the reference's training loop (per-class IoU, centre and angular distances, axis "
+                             "scale ratios; train.py:289-338) for the training and the validation set, computed on the device behind every "
+                             "step (egne_amd.scores: two small launches, no copy of a map, nothing synchronises); per epoch 'Train IoU' is "
+                             "printed and one JSON line goes to logs/<model>/<expname>/scores.jsonl under the reference's TensorBoard tags"),
 )
 _MODEL = (
     ("model", str, "ritnet_v2", "key into modelSummary.model_dict"),
@@ -60,7 +64,9 @@ _OUTPUT = (
     ("expname", str, "dev", "sub-directory of logs/<model>/"),
     ("disp", int, 0, "1: show intermediate outputs"),
     ("test_save_op_masks", int, 0, "1: write predicted masks"),
-    ("record_iou", int, 0, None),
+    ("record_iou", int, 0, "1 (test.py, needs --device_metrics 1): write the per-sample IoUs [N,3] to img/<curObj>_<method>_ious.pkl"),
+    ("device_metrics", int, 0, "1 (test.py): IoU and centre distances from the class map and the labels on the device (egne_amd.scores) "
+                               "instead of host copies of both maps per batch; the same prints and return values, bit for bit"),
     ("record_img", int, 0, None),
     ("iou_filename", str, "test.pkl", None),
     ("visual_dir", str, "iris", None),

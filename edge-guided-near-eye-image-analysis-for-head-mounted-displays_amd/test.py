@@ -29,6 +29,14 @@ def calc_acc(args, testloader, model, edge_model, device):
     from egne_amd.pipeline import TwoStagePipeline
     pipe = TwoStagePipeline(args, edge_model, torch.device(device))
     waiting = []
+    ledger = None
+    if getattr(args, "device_metrics", 0):
+        # --device_metrics 1: the class map and the labels stay on the device; one row of raw scores per sample (egne_amd.scores), one
+        # copy down behind the last batch.  DeepVOG predicts pupil / not pupil: two classes against labels == 2 (test.py:157-158)
+        from egne_amd import scores
+        ledger = scores.ScoreLedger(len(testloader) * args.batchsize, device, ncls=2 if args.model == 'deepvog' else 3)
+    elif getattr(args, "record_iou", 0):
+        print('--record_iou 1 needs --device_metrics 1: the per-sample IoUs are rows of its ledger; nothing is written')
 
     def second(batch):
         img, labels, spatialWeights, distMap, pupil_center, iris_center, elNorm, cond, imInfo = batch
@@ -74,6 +82,11 @@ def calc_acc(args, testloader, model, edge_model, device):
             redo[0] = cleared
         model.raise_on_loss_flags(flags)           # two absent classes: loss.py:132 raises in the reference
         img, labels, spatialWeights, distMap, pupil_center, iris_center, elNorm, cond, imInfo = batch
+        if ledger is not None:      # behind the redo decision: a batch that ran again is counted once, with its second result
+            lab = labels.to(device).long()
+            ledger.append((lab == 2).long() if ledger.ncls == 2 else lab, mask, elOut, elPred, pupil_center.to(device), iris_center.to(device),
+                          elNorm.to(device), cond.to(device), loss)
+            return
         predict = mask.cpu().numpy()
         cnp = cond.cpu().numpy().astype(np.float32)
         iou, _, _ = getSeg_metrics(labels.cpu().numpy(), predict, cnp[:, 1])
@@ -102,7 +115,22 @@ def calc_acc(args, testloader, model, edge_model, device):
     if r is not None and waiting:
         metrics(waiting.pop(0), r)
     assert not waiting
-    if parallel.world_size() > 1:     # frames shard over ranks (no data-path collective); only the per-batch metrics are gathered
+    if ledger is not None:
+        # the same per-batch numbers from the rows: utils.getSeg_metrics' own reduction, the flag / sum / divide of getPoint_metric, the
+        # float32 loss widened as .item() widens it
+        rows = scores.gather_rows(ledger.rows())
+        for b in scores.batches(rows):
+            ious.append(scores.seg_metrics(b)[0])
+            dists_pupil_latent.append(scores.point_metric(b, "pupil_latent", 0)[0]); dists_pupil_seg.append(scores.point_metric(b, "pupil_seg", 0)[0])
+            dists_iris_latent.append(scores.point_metric(b, "iris_latent", 1)[0]); dists_iris_seg.append(scores.point_metric(b, "iris_seg", 1)[0])
+            losses.append(float(b[0, scores.LOSS]))
+        if args.record_iou and parallel.rank() == 0:          # test.py:219-230
+            os.makedirs('img', exist_ok=True)
+            filename = os.path.join('img', '{}_{}_ious.pkl'.format(args.curObj if args.curObj is not None else 'synthetic', args.method))
+            with open(filename, 'wb') as f:
+                pickle.dump(np.ascontiguousarray(rows[:, scores.IOU:scores.IOU + 3]), f)
+            print('per-sample IoUs {} written to {}'.format(rows[:, scores.IOU:scores.IOU + 3].shape, filename))
+    elif parallel.world_size() > 1:     # frames shard over ranks (no data-path collective); only the per-batch metrics are gathered
         ious, dists_pupil_latent, dists_pupil_seg, dists_iris_latent, dists_iris_seg, losses = (
             parallel.gather_lists(v) for v in (ious, dists_pupil_latent, dists_pupil_seg, dists_iris_latent, dists_iris_seg, losses))
     ious = np.nanmean(np.stack(ious)) if ious else np.nan

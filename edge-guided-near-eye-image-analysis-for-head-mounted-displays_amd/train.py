@@ -5,6 +5,7 @@ one process per GPU (torchrun) instead of nn.DataParallel.
     python train.py --synthetic 32 --batchsize 8 --epochs 2 --setting configs/baseline_edge.yaml
     torchrun --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 train.py --curObj ... --setting ...
 """
+import json
 import os
 import pickle
 import sys
@@ -40,12 +41,15 @@ class EarlyStopping:
             self.early_stop = self.counter >= self.patience
 
 
-def lossandaccuracy(args, loader, model, edge_model, alpha, device):
+def lossandaccuracy(args, loader, model, edge_model, alpha, device, ledger=None):
     """utils.py:658-760 (the shipped version dies in np.stack([])): validation loss + mIoU.
     Under torchrun every rank validates ITS shard of the loader; the means are combined over ranks so that all
-    ranks feed the same numbers to the LR scheduler / early stopping."""
+    ranks feed the same numbers to the LR scheduler / early stopping.
+    ``ledger`` (--track_scores 1, an empty egne_amd.scores.ScoreLedger): every batch leaves its rows there instead of copying its two
+    maps to the host, and the same two numbers come from the rows, with the same weighting."""
     model.eval()
     lsum = nsamp = isum = icnt = 0.0
+    first_row = ledger.n if ledger is not None else 0
     train_products = getattr(edge_model, "f16_products", 0)
     edge_model.f16_products = 0          # validation: the 22-bit split products, as test.py
     try:
@@ -76,6 +80,10 @@ def lossandaccuracy(args, loader, model, edge_model, alpha, device):
             # batches are weighted by their sample count: under torchrun the shards (and their last batches) differ in size
             n = float(img.shape[0])
             model.raise_on_loss_flags(model.loss_flags())       # two absent classes: loss.py:132 raises in the reference
+            if ledger is not None:     # behind the redo decision: a batch that ran again is counted once
+                ledger.append(labels.to(device).long(), model.predictions(), out[4], out[1], pc.to(device), ic.to(device), eln.to(device),
+                              cond.to(device), out[3])
+                continue
             lsum += out[3].mean().item() * n
             nsamp += n
             iou = getSeg_metrics(labels.cpu().numpy(), model.predictions().cpu().numpy(), cond.cpu().numpy().astype(np.float32)[:, 1])[0]
@@ -85,6 +93,16 @@ def lossandaccuracy(args, loader, model, edge_model, alpha, device):
     finally:
         model.train()
         edge_model.f16_products = train_products
+    if ledger is not None:
+        from egne_amd import scores
+        for b in scores.batches(ledger.rows()[first_row:]):
+            n = float(len(b))
+            lsum += float(b[0, scores.LOSS]) * n
+            nsamp += n
+            iou = scores.seg_metrics(b)[0]
+            if iou == iou:
+                isum += float(iou) * n
+                icnt += n
     if nsamp == 0:
         raise RuntimeError("rank %d validated no batch (validation set too small for %d ranks?)" % (parallel.rank(), parallel.world_size()))
     sums = parallel.sum_over_ranks([lsum, nsamp, isum, icnt], device)
@@ -162,6 +180,12 @@ def main(argv=None):
     if getattr(args, "pipeline", 0):
         from egne_amd.pipeline import TwoStagePipeline
         pipe = TwoStagePipeline(args, edge_net, device)
+    tledger = vledger = None
+    if getattr(args, "track_scores", 0):
+        # the scores the reference's loop tracks per batch (train.py:289-338), as rows on the device: one ledger per set, read once per epoch
+        from egne_amd import scores
+        tledger = scores.ScoreLedger(len(trainloader) * args.batchsize, device)
+        vledger = scores.ScoreLedger(len(validObj), device)
     for epoch in range(startEp, args.epochs):
         alpha = epoch / args.epochs                                                 # helperfunctions.linVal, train.py:248
         if tsamp is not None:
@@ -175,7 +199,7 @@ def main(argv=None):
                 batch = loader.device_batch(batch, augment=True, on_cv2="device")
             img, labels, sw, dm, pc, ic, eln, cond, imInfo = batch
 
-            def rest(edge, img=img, labels=labels, sw=sw, dm=dm, pc=pc, eln=eln, cond=cond, imInfo=imInfo):
+            def rest(edge, img=img, labels=labels, sw=sw, dm=dm, pc=pc, ic=ic, eln=eln, cond=cond, imInfo=imInfo):
                 ov = check_edge and bool(edge_net.overflowed())          # (reads AND clears the plan's sticky word)
                 if check_edge and (redo_edge[0] or ov):
                     # the frozen edge network left the f16 range of its calibrated pre-scales (engine.Plan.overflowed): this edge map holds
@@ -197,20 +221,22 @@ def main(argv=None):
                     if pipe is not None:
                         pipe.sa.wait_stream(torch.cuda.current_stream())
                 optimizer.zero_grad()
-                pc_u, eln_u, cond_u = pc.to(device), eln.to(device), cond.to(device).float()
+                pc_u, ic_u, eln_u, cond_u = pc.to(device), ic, eln.to(device), cond.to(device).float()
                 if args.device_prep:    # bit-identical to the Dataset's one_hot2dist maps, 54k frames/s instead of 123 per host core
                     from egne_amd import dataprep
                     dm = dataprep.dist_maps(labels.to(device).long())
                     if args.device_prep >= 2:   # the boundary weights too (CurriculumLib.py:128-129; parity unpinned: no OpenCV to check against)
                         sw = dataprep.spatial_weights(labels.to(device).long())
                     if args.device_prep >= 3:   # the ellipse targets too: the reference's ElliFit + RANSAC on the label's boundaries (csrc/ellifit.hip)
-                        pc_u, _, eln_u, cond_u = dataprep.ellipse_targets(labels.to(device).long())
+                        pc_u, ic_u, eln_u, cond_u = dataprep.ellipse_targets(labels.to(device).long())
                 out = model(img.to(device), edge, labels.to(device).long(), pc_u, eln_u, sw.to(device),
                             dm.to(device), cond_u, imInfo[:, 2].to(device), alpha)
                 loss = out[3].mean()                                                   # train.py:285
                 loss.backward()
                 parallel.allreduce_grads(model)
                 optimizer.step()
+                if tledger is not None:     # two small launches behind the step, on the step's own stream; nothing is read back here
+                    tledger.append(labels.to(device).long(), model.predictions(), out[4], out[1], pc_u, ic_u.to(device), eln_u, cond_u, out[3])
                 return loss.detach(), model.loss_flags()
 
             if pipe is not None:
@@ -239,7 +265,23 @@ def main(argv=None):
         if pipe is not None:
             pipe.flush()                       # the last batch of the epoch
         parallel.broadcast_buffers(model)      # validate with rank 0's BatchNorm statistics (DataParallel keeps replica 0's)
-        vloss, viou = lossandaccuracy(args, validloader, model, edge_net, alpha, device)
+        if tledger is not None:
+            trows = scores.gather_rows(tledger.rows())      # (the epoch's one copy down of the training rows; every rank gets all of them)
+            tsum = scores.epoch_summary(trows)
+            if rank == 0:
+                print('Epoch:{}, Train IoU: {}'.format(epoch, np.array(tsum['train_iou'])))       # train.py:387-389
+        vloss, viou = lossandaccuracy(args, validloader, model, edge_net, alpha, device, ledger=vledger)
+        if tledger is not None:
+            vsum = scores.epoch_summary(scores.gather_rows(vledger.rows()))
+            if rank == 0:
+                # train.py:402-430 without TensorBoard: one line per epoch under its tags.  loss/train is the mean of the batches' losses
+                # (the reference divides their sum by the LAST batch index)
+                tl = [float(b[0, scores.LOSS]) for b in scores.batches(trows)]
+                with open(os.path.join(logdir, 'scores.jsonl'), 'a') as f:
+                    f.write(json.dumps({'epoch': epoch, 'train': tsum, 'valid': vsum, 'loss/train': float(np.mean(tl)) if tl else float('nan'),
+                                        'loss/valid': float(vloss)}) + '\n')
+            tledger.reset()
+            vledger.reset()
         if rank == 0:
             print('Epoch {} done in {:.1f}s: valid loss {:.4f} mIoU {:.4f}'.format(epoch, time.time() - t0, vloss, viou))
             ckpt = _entry.checkpoint_dict(model, epoch)

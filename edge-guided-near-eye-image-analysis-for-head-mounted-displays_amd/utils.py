@@ -154,7 +154,12 @@ def getSeg_metrics(y_true, y_pred, cond):
             for j, v in enumerate(present):
                 vals[v] = sc[j]
         rows.append(vals)
-    rows = np.stack(rows, axis=0)
+    return seg_metrics_of_rows(np.stack(rows, axis=0), cond)
+
+
+def seg_metrics_of_rows(rows, cond):
+    """The reduction that ends getSeg_metrics (utils.py:146-150) on a finished ``score_list`` [B,3] and a boolean ``cond``; shared
+    with egne_amd.scores, whose rows come from the device."""
     clean = rows[~cond, :]
     if len(clean) == 0:
         return np.nan, np.nan * np.ones(3), rows

@@ -1162,6 +1162,49 @@ typedef struct {
 
 int egne_conv2d_auto_kind(const egne_conv_query* q, egne_conv_choice* out);
 
+/* ---- score tracking of train.py / test.py on the device (csrc/scores.hip, egne_amd.scores) -----------------------------------
+ * What the reference computes per batch on host copies of the class map and the labels -- utils.py:120-170 (getSeg_metrics,
+ * getPoint_metric, getAng_metric) and the loop body train.py:289-338 -- from tensors that are on the device already.  Both calls
+ * queue work on `stream` and synchronise nothing.
+ *
+ * egne_seg_confusion_counts: y_true, y_pred int64 [B,H,W] (contiguous, 8-byte aligned; 16-byte loads are used when both pointers
+ *   agree modulo 16, frames of odd size included); counts uint32 [B, ncls, 3] = (n_true, n_pred, n_both) per frame and class,
+ *   zeroed by the call itself.  ncls is 2 or 3; values outside [0, ncls) count for no class.  H * W < 2^31, B <= 65535.
+ *   A workgroup takes EGNE_SCORES_CHUNK pixels of one frame (grid: chunks x frames) and adds its sums with integer atomics:
+ *   the result does not depend on the order.
+ *
+ * egne_score_rows: one row of EGNE_SCORE_FIELDS float64 per sample, written at ledger[row_offset + i].  All vectors float32:
+ *   elOut, elPred [B,10]; pupil_center, iris_center [B,2] in pixels; elNorm [B,2,5]; cond [B,ncond] (non-zero = set, ncond >= 2);
+ *   loss_terms: one float32 read on the device (element 0), or NULL (the field is NaN).  Fields:
+ *     IOU + c            NaN if cond[:,1] is set or class c is absent from the truth, else n_both / (n_true + n_pred - n_both)
+ *     DIST_*             raw (unflagged) centre distances in pixels, float32 arithmetic as utils.unnormPts + getPoint_metric, widened:
+ *                        pupil: pupil_center against elOut[:,5:7] (latent) / elPred[:,5:7] (seg); iris: iris_center against [:,0:2]
+ *     ANG_IRIS / _PUPIL  float32 |elNorm[:,k,4] - elOut[:,4 or 9]| widened, times 180 / pi in float64 (np.rad2deg)
+ *     SCALE_IRIS/_PUPIL  float32 sqrt((a_gt^2 + b_gt^2) / (a_pred^2 + b_pred^2)) from elNorm[:,k,2:4] and elOut[:,2:4 or 7:9], widened
+ *     COND0, COND1       0 or 1
+ *     LOSS, BATCH        loss_terms[0] widened; batch_no as passed
+ *     SAMPLE             index of the sample in its batch */
+#define EGNE_SCORES_CHUNK 2048
+#define EGNE_SCORE_IOU 0
+#define EGNE_SCORE_DIST_PUPIL_LATENT 3
+#define EGNE_SCORE_DIST_PUPIL_SEG 4
+#define EGNE_SCORE_DIST_IRIS_LATENT 5
+#define EGNE_SCORE_DIST_IRIS_SEG 6
+#define EGNE_SCORE_ANG_IRIS 7
+#define EGNE_SCORE_ANG_PUPIL 8
+#define EGNE_SCORE_SCALE_IRIS 9
+#define EGNE_SCORE_SCALE_PUPIL 10
+#define EGNE_SCORE_COND0 11
+#define EGNE_SCORE_COND1 12
+#define EGNE_SCORE_LOSS 13
+#define EGNE_SCORE_BATCH 14
+#define EGNE_SCORE_SAMPLE 15
+#define EGNE_SCORE_FIELDS 16
+int egne_seg_confusion_counts(const void* y_true, const void* y_pred, int B, int H, int W, int ncls, void* counts, void* stream);
+int egne_score_rows(const void* counts, int B, int ncls, const void* elOut, const void* elPred, const void* pupil_center,
+                    const void* iris_center, const void* elNorm, const void* cond, int ncond, const void* loss_terms, int H, int W,
+                    int batch_no, void* ledger, int64_t row_offset, int64_t capacity_rows, void* stream);
+
 const char* egne_last_error(void);
 int egne_version(void);
 int egne_sizeof(int which);   /* 0 egne_conv_desc, 1 egne_loss_desc, 2 egne_bdcn_tail_desc, 3 egne_dst, 4 egne_conv_query, 5 egne_conv_choice */
