@@ -67,6 +67,12 @@ _OUTPUT = (
     ("record_iou", int, 0, "1 (test.py, needs --device_metrics 1): write the per-sample IoUs [N,3] to img/<curObj>_<method>_ious.pkl"),
     ("device_metrics", int, 0, "1 (test.py): IoU and centre distances from the class map and the labels on the device (egne_amd.scores) "
                                "instead of host copies of both maps per batch; the same prints and return values, bit for bit"),
+    ("ellipse_metrics", int, 0, "1 (test.py, needs --device_metrics 1): score the ellipses of elPred against elNorm on the device "
+                                "(egne_amd.scores.EllipseLedger): the reference's bounding-box IoU and absolute parameter errors "
+                                "(test.py:108-155, off in its source), the IoU of the ellipses themselves and of either against the class "
+                                "map; with --record_iou 1 the per-sample rows go to img/<curObj>_<method>_ellipses.pkl"),
+    ("ellipse_search", int, 0, "1 (test.py, needs --ellipse_metrics 1): score the ellipses after the search against the predicted class "
+                               "map (the reference's search_flag) instead of the regressed ones"),
     ("record_img", int, 0, None),
     ("iou_filename", str, "test.pkl", None),
     ("visual_dir", str, "iris", None),
@@ -83,6 +89,15 @@ def build_parser():
         for name, typ, default, text in table:
             grp.add_argument("--" + name, type=typ, default=default, help=text)
     return p
+
+
+def ellipse_metrics_note(args):
+    """What test.py says when the ellipse flags ask for something their prerequisites do not give (it then does without), or None."""
+    if getattr(args, "ellipse_metrics", 0) and not getattr(args, "device_metrics", 0):
+        return '--ellipse_metrics 1 needs --device_metrics 1: the ellipse scores are rows of a device ledger; nothing is scored'
+    if getattr(args, "ellipse_search", 0) and not getattr(args, "ellipse_metrics", 0):
+        return '--ellipse_search 1 needs --ellipse_metrics 1: without it no ellipse is scored; nothing is searched'
+    return None
 
 
 def parse_args(argv=None):

@@ -16,7 +16,7 @@ import numpy as np  # noqa: E402
 import torch  # noqa: E402
 from torch.utils.data import DataLoader  # noqa: E402
 
-from egne_amd.args import parse_args  # noqa: E402
+from egne_amd.args import ellipse_metrics_note, parse_args  # noqa: E402
 from egne_amd.utils import calc_edge, getPoint_metric, getSeg_metrics  # noqa: E402
 
 
@@ -37,6 +37,15 @@ def calc_acc(args, testloader, model, edge_model, device):
         ledger = scores.ScoreLedger(len(testloader) * args.batchsize, device, ncls=2 if args.model == 'deepvog' else 3)
     elif getattr(args, "record_iou", 0):
         print('--record_iou 1 needs --device_metrics 1: the per-sample IoUs are rows of its ledger; nothing is written')
+    # --ellipse_metrics 1: the block the reference keeps behind bbox_iou_flag (test.py:108-155), one more row per sample on the device.
+    # DeepVOG predicts the pupil only, as class 1 of its two-class map: the iris columns stay NaN
+    ell_ledger = None
+    calc_acc.last_ellipse_summary = None
+    note = ellipse_metrics_note(args)
+    if note:
+        print(note)
+    elif getattr(args, "ellipse_metrics", 0):
+        ell_ledger = scores.EllipseLedger(len(testloader) * args.batchsize, device, classes=(-1, 1) if args.model == 'deepvog' else (1, 2))
 
     def second(batch):
         img, labels, spatialWeights, distMap, pupil_center, iris_center, elNorm, cond, imInfo = batch
@@ -86,6 +95,8 @@ def calc_acc(args, testloader, model, edge_model, device):
             lab = labels.to(device).long()
             ledger.append((lab == 2).long() if ledger.ncls == 2 else lab, mask, elOut, elPred, pupil_center.to(device), iris_center.to(device),
                           elNorm.to(device), cond.to(device), loss)
+            if ell_ledger is not None:
+                ell_ledger.append(mask, elPred, elNorm.to(device), cond.to(device), search=bool(args.ellipse_search))
             return
         predict = mask.cpu().numpy()
         cnp = cond.cpu().numpy().astype(np.float32)
@@ -130,6 +141,14 @@ def calc_acc(args, testloader, model, edge_model, device):
             with open(filename, 'wb') as f:
                 pickle.dump(np.ascontiguousarray(rows[:, scores.IOU:scores.IOU + 3]), f)
             print('per-sample IoUs {} written to {}'.format(rows[:, scores.IOU:scores.IOU + 3].shape, filename))
+        if ell_ledger is not None:
+            ell_rows = scores.gather_rows(ell_ledger.rows(), scores.ELL_FIELDS, scores.ELL_BATCH)
+            calc_acc.last_ellipse_summary = scores.ellipse_summary(ell_rows)
+            if args.record_iou and parallel.rank() == 0:      # the job of the reference's record_new_parameters (test.py:142-147)
+                filename = os.path.join('img', '{}_{}_ellipses.pkl'.format(args.curObj if args.curObj is not None else 'synthetic', args.method))
+                with open(filename, 'wb') as f:
+                    pickle.dump({'fields': scores.ell_field_names(), 'rows': np.ascontiguousarray(ell_rows)}, f)
+                print('per-sample ellipse scores {} written to {}'.format(ell_rows.shape, filename))
     elif parallel.world_size() > 1:     # frames shard over ranks (no data-path collective); only the per-batch metrics are gathered
         ious, dists_pupil_latent, dists_pupil_seg, dists_iris_latent, dists_iris_seg, losses = (
             parallel.gather_lists(v) for v in (ious, dists_pupil_latent, dists_pupil_seg, dists_iris_latent, dists_iris_seg, losses))
@@ -141,6 +160,16 @@ def calc_acc(args, testloader, model, edge_model, device):
     print('Segmentation PUPIL dist. Med: {}, STD: {}'.format(np.nanmedian(dists_pupil_seg), np.nanstd(dists_pupil_seg)))
     print('Latent space IRIS dist. Med: {}, STD: {}'.format(np.nanmedian(dists_iris_latent), np.nanstd(dists_iris_latent)))
     print('Segmentation IRIS dist. Med: {}, STD: {}'.format(np.nanmedian(dists_iris_seg), np.nanstd(dists_iris_seg)))
+    if calc_acc.last_ellipse_summary is not None:
+        s = calc_acc.last_ellipse_summary
+        has_iris = args.model != 'deepvog'
+        print('Bounding box Pupil IoU. Mean : {}'.format(s['bbiou_pupil']))         # test.py:240-247
+        if has_iris: print('Bounding box Iris IoU. Mean : {}'.format(s['bbiou_iris']))
+        print('ABS Pupil parameters : ', s['para_pupil'])
+        if has_iris: print('ABS Iris parameters : ', s['para_iris'])
+        for name in (('pupil', 'iris') if has_iris else ('pupil',)):
+            print('Ellipse area {} IoU against ground truth. Mean : {}'.format(name.upper(), s['ell_iou_' + name]))
+            print('Class map {} IoU. Scored ellipse : {}, ground-truth ellipse : {}'.format(name.upper(), s['map_iou_pred_' + name], s['map_iou_gt_' + name]))
     return ious, np.nanmedian(dists_pupil_seg), np.nanmedian(dists_iris_seg), float(np.mean(losses))
 
 

@@ -265,16 +265,20 @@ def ellipse_seeds_from_pred(elPred, H, W):
     return init, fo, cl
 
 
-def fit_ellipses_from_pred(mask, elPred, out=None):
+def fit_ellipses_from_pred(mask, elPred, out=None, classes=None):
     """The fit stage of evaluate.py:135-166 with no host hop: seeds from ``elPred`` on the device, both searches of
     every frame in one launch.  Returns a DEVICE tensor [F,2,5] float64 (iris, pupil) x (cx,cy,a,b,theta); nothing
-    here synchronises -- the caller decides when to read it."""
+    here synchronises -- the caller decides when to read it.  ``classes``: the class of the map the iris and the pupil are
+    searched against (default (1, 2)); a negative one leaves that search out, its row is NaN."""
     require_cuda(mask, "mask")
     L = _lib.lib()
     F, H, W = mask.shape
     if elPred.shape[0] != F:
         raise ValueError("fit_ellipses_from_pred: %d ellipse rows for %d class maps" % (elPred.shape[0], F))
     init, fo, cl = ellipse_seeds_from_pred(elPred, H, W)
+    if classes is not None and tuple(classes) != (1, 2):
+        cl = torch.tensor([int(classes[0]), int(classes[1])], dtype=torch.int32, device=mask.device).repeat(F)
+        fo = torch.where(cl < 0, torch.full_like(fo, -1), fo)
     if out is None:
         out = torch.empty((F, 2, 5), dtype=torch.float64, device=mask.device)
     xs, ys = _mesh_axes(H, W, mask.device)

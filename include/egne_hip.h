@@ -1205,6 +1205,60 @@ int egne_score_rows(const void* counts, int B, int ncls, const void* elOut, cons
                     const void* iris_center, const void* elNorm, const void* cond, int ncond, const void* loss_terms, int H, int W,
                     int batch_no, void* ledger, int64_t row_offset, int64_t capacity_rows, void* stream);
 
+/* ---- ellipse scores of test.py against ground truth (csrc/ellipse_scores.hip, egne_amd.scores.EllipseLedger) ------------------
+ * The block the reference keeps behind bbox_iou_flag (test.py:108-155): per sample and region (0 iris, 1 pupil) the IoU of the
+ * rotated bounding boxes of the scored and the ground-truth ellipse (calc_box_iou.py:13-54) and the absolute differences of their
+ * parameters; also the IoU of the two ellipses themselves and of either against the class map.  All calls queue work on `stream`,
+ * synchronise nothing, use no atomics and give the same bits on every run.
+ *
+ * egne_ellipse_pair_scores: one row of EGNE_ELLSCORE_FIELDS float64 per sample at ledger[row_offset + i]; one workgroup per (sample,
+ *   region).  elNorm [B,2,5] float32, the ground truth on the normalised mesh; pred_px [B,2,5] float64, the scored ellipses in
+ *   pixels (cx, cy, a, b, theta) -- from egne_ellipse_init_from_pred, from egne_ellipse_fit or from anywhere else; mask [B,H,W]
+ *   int64 class map; cond [B,ncond] float32 (non-zero = set, ncond >= 2); cls_iris / cls_pupil: the class of the map each region
+ *   is held against, negative = the region is not scored and its fields are NaN; xs[W] / ys[H]: the mesh axes as egne_ellipse_fit
+ *   takes them.  H, W from 2 up to the limit of egne_ellipse_fit.  The ground-truth pixel ellipse is the transform of
+ *   egne_ellipse_init_from_pred (the same device function).  Fields of a region, at r * EGNE_ELLSCORE_REGION_FIELDS:
+ *     ELL_PRED, ELL_GT     5 each: the two pixel ellipses
+ *     CORNERS_PRED, _GT    8 each: (x0, y0, ..., x3, y3) of calc_bbox in float64 -- centre rotated by -theta, corners (-a,-b), (-a,+b),
+ *                          (+a,+b), (+a,-b) around it, each rotated by theta -- converted to int32 as NumPy converts (truncation toward
+ *                          zero; NaN and values outside int32 give INT_MIN)
+ *     BOX_IOU, _AND, _OR   n_and / n_or in float64 (NaN for 0 / 0) and the two counts over the H x W canvas.  A pixel (x, y), 0 <= x < W,
+ *                          0 <= y < H, belongs to a box iff for each of its four edges k -> k+1 the cross product
+ *                          (x[k+1]-x[k]) (y-y[k]) - (y[k+1]-y[k]) (x-x[k]), in exact integers, has the sign of the box's signed area or
+ *                          is zero; a box without area holds the pixels exactly on its four segments.  (cv2.fillPoly agrees away
+ *                          from the edges; which edge pixels it sets is not restated.)
+ *     PARA                 5: |ELL_PRED - ELL_GT|, the angle in radians
+ *     AREA                 3: pixels inside the scored ellipse, inside the ground-truth ellipse, inside both -- the membership rule of
+ *                          calc_ell_iou (utils.py:185-196) through the device functions of egne_ellipse_fit
+ *     MAP_PRED, MAP_GT     3 each: (pixels of the class, pixels of the ellipse, pixels of both) as egne_ellipse_iou_counts counts them
+ *   and per row COND0, COND1 (0 or 1), BATCH (batch_no as passed), SAMPLE (index in the batch).
+ *
+ * egne_ellipse_box_corners: ell_px [n,5] float64 -> corners [n,8] int32.  egne_box_iou_counts: corners_a, corners_b [n,8] int32 ->
+ *   out [n,3] float64 (IoU, n_and, n_or) on an H x W canvas (H * W < 2^31).  The device functions of the call above, for tests and
+ *   for boxes from elsewhere. */
+#define EGNE_ELLSCORE_ELL_PRED 0
+#define EGNE_ELLSCORE_ELL_GT 5
+#define EGNE_ELLSCORE_CORNERS_PRED 10
+#define EGNE_ELLSCORE_CORNERS_GT 18
+#define EGNE_ELLSCORE_BOX_IOU 26
+#define EGNE_ELLSCORE_BOX_AND 27
+#define EGNE_ELLSCORE_BOX_OR 28
+#define EGNE_ELLSCORE_PARA 29
+#define EGNE_ELLSCORE_AREA 34
+#define EGNE_ELLSCORE_MAP_PRED 37
+#define EGNE_ELLSCORE_MAP_GT 40
+#define EGNE_ELLSCORE_REGION_FIELDS 43
+#define EGNE_ELLSCORE_COND0 86
+#define EGNE_ELLSCORE_COND1 87
+#define EGNE_ELLSCORE_BATCH 88
+#define EGNE_ELLSCORE_SAMPLE 89
+#define EGNE_ELLSCORE_FIELDS 90
+int egne_ellipse_pair_scores(const void* elNorm, const void* pred_px, const void* mask, const void* cond, int ncond, int B, int H, int W,
+                             int cls_iris, int cls_pupil, const void* xs, const void* ys, int batch_no, void* ledger,
+                             int64_t row_offset, int64_t capacity_rows, void* stream);
+int egne_ellipse_box_corners(const void* ell_px, int n, void* corners, void* stream);
+int egne_box_iou_counts(const void* corners_a, const void* corners_b, int n, int H, int W, void* out, void* stream);
+
 const char* egne_last_error(void);
 int egne_version(void);
 int egne_sizeof(int which);   /* 0 egne_conv_desc, 1 egne_loss_desc, 2 egne_bdcn_tail_desc, 3 egne_dst, 4 egne_conv_query, 5 egne_conv_choice */
