@@ -218,6 +218,8 @@ SIGNATURES = {
     "egne_ellipse_pair_scores": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp, vp, i32, vp, i64, i64, vp]),
     "egne_ellipse_box_corners": (i32, [vp, i32, vp, vp]),
     "egne_box_iou_counts": (i32, [vp, vp, i32, i32, i32, vp, vp]),
+    "egne_disp_grid_workspace_bytes": (i64, [i32]),
+    "egne_disp_grid": (i32, [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp]),
     "egne_last_error": (C.c_char_p, []),
     "egne_version": (i32, []),
     "egne_sizeof": (i32, [i32]),

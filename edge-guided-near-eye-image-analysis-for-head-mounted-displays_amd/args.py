@@ -62,7 +62,12 @@ _DATA = (
 )
 _OUTPUT = (
     ("expname", str, "dev", "sub-directory of logs/<model>/"),
-    ("disp", int, 0, "1: show intermediate outputs"),
+    ("disp", int, 0, "1: prediction overlay grids drawn on the device (egne_amd.dispgrid, the reference's generateImageGrid: the frame "
+                     "histogram-equalised, the predicted classes painted in, the predicted ellipses outlined).  test.py writes the grid "
+                     "of the first four frames of every batch to img/<curObj or 'synthetic'>_<method>_disp/batch_%%05d.jpg; train.py "
+                     "writes the grid of every epoch's last training batch (the reference's train/op image) to "
+                     "logs/<model>/<expname>/disp/epoch_%%03d.jpg, rank 0 only.  Nothing is drawn per training batch: there is no "
+                     "window to show it in"),
     ("test_save_op_masks", int, 0, "1: write predicted masks"),
     ("record_iou", int, 0, "1 (test.py, needs --device_metrics 1): write the per-sample IoUs [N,3] to img/<curObj>_<method>_ious.pkl"),
     ("device_metrics", int, 0, "1 (test.py): IoU and centre distances from the class map and the labels on the device (egne_amd.scores) "

@@ -21,7 +21,8 @@ from egne_amd.utils import calc_edge, getPoint_metric, getSeg_metrics  # noqa: E
 
 
 def calc_acc(args, testloader, model, edge_model, device):
-    """test.py:31-252 without the visualisation: per batch edge -> model -> argmax -> metrics."""
+    """test.py:31-252: per batch edge -> model -> argmax -> metrics; with --disp 1 the overlay grid of every batch (test.py:165-181) goes
+    to a JPEG file instead of a window."""
     ious, dists_pupil_latent, dists_pupil_seg, dists_iris_latent, dists_iris_seg, losses = [], [], [], [], [], []
     model.eval()
     # the edge network of batch i+1 runs next to the model of batch i (egne_amd.pipeline), and the host computes the metrics of
@@ -60,6 +61,14 @@ def calc_acc(args, testloader, model, edge_model, device):
         return run
 
     redo = [False]
+    disp_dir = None
+    if getattr(args, "disp", 0) and parallel.rank() == 0:
+        # --disp 1: the grid the reference shows for every batch (test.py:165-181: elPred, override, elNorm), drawn and encoded on the
+        # device (egne_amd.dispgrid), one file per batch
+        from egne_amd import dispgrid
+        disp_dir = os.path.join('img', '{}_{}_disp'.format(args.curObj if args.curObj is not None else 'synthetic', args.method))
+        os.makedirs(disp_dir, exist_ok=True)
+    drawn = [0]
 
     def metrics(batch, r):
         (mask, elPred, elOut, loss, flags), done = r
@@ -91,6 +100,10 @@ def calc_acc(args, testloader, model, edge_model, device):
             redo[0] = cleared
         model.raise_on_loss_flags(flags)           # two absent classes: loss.py:132 raises in the reference
         img, labels, spatialWeights, distMap, pupil_center, iris_center, elNorm, cond, imInfo = batch
+        if disp_dir is not None:    # behind the redo decision: a batch that ran again is drawn once, with its second result
+            u8 = dispgrid.script_grid(args.model, img.to(device), mask, elPred, cond.to(device), elNorm.to(device), override=True)
+            dispgrid.save_grid(os.path.join(disp_dir, 'batch_%05d.jpg' % drawn[0]), u8)
+            drawn[0] += 1
         if ledger is not None:      # behind the redo decision: a batch that ran again is counted once, with its second result
             lab = labels.to(device).long()
             ledger.append((lab == 2).long() if ledger.ncls == 2 else lab, mask, elOut, elPred, pupil_center.to(device), iris_center.to(device),

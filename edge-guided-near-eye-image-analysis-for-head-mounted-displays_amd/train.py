@@ -186,6 +186,18 @@ def main(argv=None):
         from egne_amd import scores
         tledger = scores.ScoreLedger(len(trainloader) * args.batchsize, device)
         vledger = scores.ScoreLedger(len(validObj), device)
+    disp_dir, disp_u8 = None, [None]
+    if getattr(args, "disp", 0) and rank == 0:
+        # --disp 1: the reference's train/op image (train.py:378-385, :433): the grid of the epoch's last training batch with the regressed
+        # ellipses elOut, drawn on the device behind that step and written once per epoch; nothing per batch (there is no window)
+        from egne_amd import dispgrid
+        disp_dir = os.path.join(logdir, 'disp')
+        os.makedirs(disp_dir, exist_ok=True)
+    last_bt = len(trainloader) - 1            # the last step of an epoch, as the breaks below leave it
+    if args.overfit:
+        last_bt = min(last_bt, args.overfit - 1)
+    if args.test_normal:
+        last_bt = min(last_bt, 20)
     for epoch in range(startEp, args.epochs):
         alpha = epoch / args.epochs                                                 # helperfunctions.linVal, train.py:248
         if tsamp is not None:
@@ -199,7 +211,7 @@ def main(argv=None):
                 batch = loader.device_batch(batch, augment=True, on_cv2="device")
             img, labels, sw, dm, pc, ic, eln, cond, imInfo = batch
 
-            def rest(edge, img=img, labels=labels, sw=sw, dm=dm, pc=pc, ic=ic, eln=eln, cond=cond, imInfo=imInfo):
+            def rest(edge, img=img, labels=labels, sw=sw, dm=dm, pc=pc, ic=ic, eln=eln, cond=cond, imInfo=imInfo, bt=bt):
                 ov = check_edge and bool(edge_net.overflowed())          # (reads AND clears the plan's sticky word)
                 if check_edge and (redo_edge[0] or ov):
                     # the frozen edge network left the f16 range of its calibrated pre-scales (engine.Plan.overflowed): this edge map holds
@@ -237,6 +249,9 @@ def main(argv=None):
                 optimizer.step()
                 if tledger is not None:     # two small launches behind the step, on the step's own stream; nothing is read back here
                     tledger.append(labels.to(device).long(), model.predictions(), out[4], out[1], pc_u, ic_u.to(device), eln_u, cond_u, out[3])
+                if disp_dir is not None and bt == last_bt:
+                    # queued here, on the stream this step ran on (under --pipeline 1 the pipeline's): the class map and elOut are this step's
+                    disp_u8[0] = dispgrid.script_grid(args.model, img.to(device), model.predictions(), out[4], cond_u, eln_u, override=True)
                 return loss.detach(), model.loss_flags()
 
             if pipe is not None:
@@ -264,6 +279,9 @@ def main(argv=None):
                 parallel.mean_loss(loss.detach())
         if pipe is not None:
             pipe.flush()                       # the last batch of the epoch
+        if disp_u8[0] is not None:             # (the streams are joined: pipe.flush above, or the synchronised loop)
+            dispgrid.save_grid(os.path.join(disp_dir, 'epoch_%03d.jpg' % epoch), disp_u8[0])
+            disp_u8[0] = None
         parallel.broadcast_buffers(model)      # validate with rank 0's BatchNorm statistics (DataParallel keeps replica 0's)
         if tledger is not None:
             trows = scores.gather_rows(tledger.rows())      # (the epoch's one copy down of the training rows; every rank gets all of them)

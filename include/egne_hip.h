@@ -1259,6 +1259,50 @@ int egne_ellipse_pair_scores(const void* elNorm, const void* pred_px, const void
 int egne_ellipse_box_corners(const void* ell_px, int n, void* corners, void* stream);
 int egne_box_iou_counts(const void* corners_a, const void* corners_b, int n, int H, int W, void* out, void* stream);
 
+/* ---- prediction overlay grid of train.py / test.py --disp 1 (csrc/dispgrid.hip, egne_amd.dispgrid.image_grid) -------------------
+ * The reference's generateImageGrid (utils.py:206-399): the first n = min(count, B) frames of a batch, histogram-equalised, the
+ * predicted classes painted in, the predicted ellipses outlined, tiled as torchvision.utils.make_grid(nrow, padding=2) tiles them.
+ * The call queues on `stream`, synchronises nothing and can be captured in a graph; only integer atomics: the same bits on every run.
+ *
+ * img [B,H,W] float32; mask [B,H,W] int64 class map; el, el_gt [B,2,5] float32 normalised (iris, pupil) ellipses (el_gt may be null
+ * unless draw_gt); cond [B,ncond] float32 or null (ncond >= 2); cos_sin float64 [2,720]: cos t then sin t of
+ * t = linspace(0, 2 pi, 720, endpoint=False), made by the host; grid float32 [3,Hg,Wg]; bgr_u8 uint8 [Hg,Wg,3] or null; status
+ * int32 [n]; workspace: egne_disp_grid_workspace_bytes(n) bytes.  H, W >= 6, H * W <= 2^30, n <= 65535.
+ *
+ * Per frame i < n (the reference's order of operations, utils.py:269-350), pinned by the reference:
+ *   mn = min, mx = max of the frame in float32; u = trunc_to_u8(fl32(fl32(255 * fl32(x - mn)) / fl32(mx - mn))), IEEE float32 with a
+ *   correctly rounded division; e = equalizeHist(u); e = e - min(e) in uint8; v = float32(double(e) / double(max(e))); all three
+ *   channels start at v.  The frame is painted iff override != 0, or cond is given and cond[i,1] == 0: class 1 pixels become
+ *   (0, 255, 0), class 2 pixels (255, 255, 0) -- 255 in an image whose grey lies in [0, 1], as the reference writes it --, then with
+ *   draw_gt the two ground-truth outlines in (0, 102, 255) (the reference's commented-out lines), then the iris outline in
+ *   (0, 0, 255), then the pupil outline in (255, 0, 0): later paints win.  Outline rows are clipped, not dropped:
+ *   row = min(max(row, 6), H - 6), col = min(max(col, 6), W - 6) (ndarray.clip taken literally, also where H - 6 < 6).
+ * This project's rules (the reference calls OpenCV, scikit-image and torchvision there):
+ *   equalizeHist by OpenCV's published rule: 256-bin histogram of u, i0 its first occupied bin; if bin i0 holds every pixel the output
+ *     is i0 everywhere; otherwise scale = 255.f / float(total - hist[i0]), lut[i0] = 0 and, for k > i0,
+ *     lut[k] = round_half_even(float(sum_{i0 < j <= k} hist[j]) * scale) saturated to 0..255; e = lut[u].
+ *   outline pixels: the pixel ellipse is the transform of egne_ellipse_init_from_pred (the same device function) of the widened
+ *     float32 parameters; centre and axes are truncated toward zero, the angle is kept; 720 samples
+ *     x = cx + a cos t cos th - b sin t sin th, y = cy + a cos t sin th + b sin t cos th in float64 (evaluate._draw_ellipse), each
+ *     rounded to the nearest integer, ties to even, then clipped as above.  An ellipse whose pixel parameters are not finite or
+ *     whose truncated axes are below 1 is not drawn; its status bit is set.
+ *   layout: n == 1: the frame itself, [3,H,W].  Otherwise xm = min(nrow, n), ym = ceil(n / xm), grid [3, ym (H+2) + 2, xm (W+2) + 2],
+ *     zero everywhere, frame k at row (k / xm) (H+2) + 2, column (k % xm) (W+2) + 2.
+ *   bgr_u8 = rint(255 * min(max(g, 0), 1)) in float32, channels reversed: how an imshow of the grid looks.
+ * status[i]: bit 0: the frame is constant (mx == mn; the reference divides by zero): grey 0.  Bit 1: the frame holds a non-finite
+ *   pixel; its pixels are then unspecified (but the same on every run).  Bits 2, 3: the iris / pupil outline was skipped; bits 4, 5: the
+ *   ground-truth iris / pupil outline was skipped (only outlines that were asked for set a bit). */
+#define EGNE_DISPGRID_CONSTANT 1
+#define EGNE_DISPGRID_NONFINITE 2
+#define EGNE_DISPGRID_SKIP_IRIS 4
+#define EGNE_DISPGRID_SKIP_PUPIL 8
+#define EGNE_DISPGRID_SKIP_GT_IRIS 16
+#define EGNE_DISPGRID_SKIP_GT_PUPIL 32
+int64_t egne_disp_grid_workspace_bytes(int frames);
+int egne_disp_grid(const void* img, const void* mask, const void* el, const void* el_gt, const void* cond, int ncond, int B, int H, int W,
+                   int override_, int draw_gt, int count, int nrow, const void* cos_sin, void* grid, void* bgr_u8, void* status,
+                   void* workspace, void* stream);
+
 const char* egne_last_error(void);
 int egne_version(void);
 int egne_sizeof(int which);   /* 0 egne_conv_desc, 1 egne_loss_desc, 2 egne_bdcn_tail_desc, 3 egne_dst, 4 egne_conv_query, 5 egne_conv_choice */
