@@ -220,6 +220,7 @@ SIGNATURES = {
     "egne_box_iou_counts": (i32, [vp, vp, i32, i32, i32, vp, vp]),
     "egne_disp_grid_workspace_bytes": (i64, [i32]),
     "egne_disp_grid": (i32, [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp]),
+    "egne_labels_from_annotations": (i32, [vp, vp, i32, i32, i32, vp, vp, vp, vp]),
     "egne_last_error": (C.c_char_p, []),
     "egne_version": (i32, []),
     "egne_sizeof": (i32, [i32]),

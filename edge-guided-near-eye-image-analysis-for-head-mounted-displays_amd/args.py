@@ -58,7 +58,12 @@ _DATA = (
                               "weights, distance maps, ellipse normalisation); --synthetic N then uses SyntheticRawEyes, otherwise "
                               "--raw_archive names the data"),
     ("raw_archive", str, None, "with --device_loader 1: an .npz with the arrays of the reference's H5 archives (Images, Masks_noSkin, "
-                               "pupil_loc, Fits_pupil, Fits_iris; egne_amd.loader.RawArchive)"),
+                               "pupil_loc, Fits_pupil, Fits_iris; egne_amd.loader.RawArchive), or one that holds the TEyeD annotations "
+                               "instead of masks (ann_ball, ann_iris, ann_pupil, ann_lid; egne_amd.loader.AnnotationArchive: the labels "
+                               "are then painted on the GPU per batch).  python -m egne_amd.make_archive writes either kind"),
+    ("loader_size", str, "240x320", "with --device_loader 1: pad2Size's canvas ROWSxCOLUMNS (the reference trains its 480x640 archives "
+                                    "with 480x640 and --loader_scale 0.5)"),
+    ("loader_scale", float, 0.0, "with --device_loader 1: scaleFn's factor behind the pad (0: none)"),
 )
 _OUTPUT = (
     ("expname", str, "dev", "sub-directory of logs/<model>/"),
@@ -105,8 +110,18 @@ def ellipse_metrics_note(args):
     return None
 
 
+def loader_geometry(args):
+    """(size, scale) of loader.device_batch from --loader_size / --loader_scale."""
+    try:
+        r, c = (int(v) for v in str(getattr(args, "loader_size", "240x320")).lower().split("x"))
+    except ValueError:
+        raise SystemExit('--loader_size must be ROWSxCOLUMNS, e.g. 480x640')
+    return (r, c), (float(getattr(args, "loader_scale", 0.0)) or False)
+
+
 def parse_args(argv=None):
     args = build_parser().parse_args(argv)
+    loader_geometry(args)
     if args.device_loader and not args.synthetic and not args.raw_archive:
         raise SystemExit('--device_loader 1 needs --raw_archive PATH (or --synthetic N)')
     if args.curObj is None and not args.synthetic and not (args.device_loader and args.raw_archive):

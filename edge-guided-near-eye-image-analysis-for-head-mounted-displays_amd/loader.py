@@ -15,6 +15,10 @@ the GPU, in the reference's order of operations:
 Raw sample (tuple, what readImage returns): image uint8 [r,c]; label int8 [r,c] (stored classes 0..3, -1 everywhere when absent);
 elParam float64 [2,5] (iris first, -1 when absent); pupil_center float64 [2]; cond bool [4]; imInfo int64 [3].
 
+An archive may hold the TEyeD ANNOTATIONS instead of label planes (AnnotationArchive; ``python -m egne_amd.make_archive`` writes
+either kind): ``collate_annotated`` then stacks an AnnotBatch, whose ~0.6 KB record per frame is uploaded in place of the int8 plane,
+and ``device_batch`` paints the labels on the device (dataprep.labels_from_annotations) in front of the same five stages.
+
 PARITY: the Lanczos resize of ``scale`` is evaluate.resize_lanczos4 (same device code as the evaluate.py front end), whose parity
 with cv2.resize is UNPINNED (OpenCV quantises the tap weights, this float64 restatement does not); the nearest-neighbour label resize
 and everything else of the stage are exact.  spatial_weights and the cv2 branches of the augmentation carry their own notes.
@@ -31,6 +35,10 @@ RawBatch = collections.namedtuple("RawBatch", "images labels src_hw elParam pupi
 RawBatch.__doc__ = """A collated batch of raw samples (host NumPy arrays): images uint8 and labels int8 [B,Rmax,Cmax], every frame in
 the top-left corner of its slot and zero-padded; src_hw int32 [B,2] its (rows, columns); elParam float64 [B,2,5]; pupil_center
 float64 [B,2]; cond bool [B,4]; imInfo int64 [B,3]."""
+
+AnnotBatch = collections.namedtuple("AnnotBatch", "images records src_hw elParam pupil_center cond imInfo")
+AnnotBatch.__doc__ = """A collated batch of annotated samples (host NumPy arrays): a RawBatch whose label planes are replaced by
+``records`` int32 [B,150] (dataprep.pack_annotations); cond[:,1] is False here and decided on the device from the painted labels."""
 
 
 def read_cond(pupil_center, mask, pupil_param, iris_param):
@@ -102,14 +110,62 @@ class RawArchive(torch.utils.data.Dataset):
         return (img, mask.astype(np.int8), np.stack([iris, pupil]), pc, read_cond(pc, mask, pupil, iris), self.imList[i].numpy().copy())
 
 
+class AnnotationArchive(torch.utils.data.Dataset):
+    """An ``.npz`` file that holds TEyeD annotations instead of label planes: Images uint8 [N,r,c], ann_ball [N,3] = (r, cx, cy),
+    ann_iris and ann_pupil [N,5] = (angle in degrees, cx, cy, full width, full height), ann_lid [N,n,2], float64 as the annotation
+    files hold them (``make_archive --store annotations``).  A sample is (image, record int32 [150], elParam [2,5] iris first,
+    pupil_center [2], cond [4], imInfo [3]); the ellipses and the centre are dataprep.annotation_fits of the rows, the record is
+    dataprep.pack_annotations of them.  ``index``: the frame numbers to serve (default: all)."""
+
+    NAMES = ("Images", "ann_ball", "ann_iris", "ann_pupil", "ann_lid")
+
+    def __init__(self, path, index=None, dataset_id=0):
+        with np.load(path) as z:
+            missing = [k for k in self.NAMES if k not in z.files]
+            if missing:
+                raise ValueError("AnnotationArchive %s: arrays %s are missing" % (path, ", ".join(missing)))
+            self.a = {k: z[k] for k in self.NAMES}
+        a, n = self.a, len(self.a["Images"])
+        self.records = dataprep.pack_annotations(a["ann_ball"], a["ann_iris"], a["ann_pupil"], a["ann_lid"]) if n else np.zeros((0, 150), np.int32)
+        self.pupil_loc, self.fits_pupil, self.fits_iris = dataprep.annotation_fits(a["ann_iris"], a["ann_pupil"])
+        self.index = np.arange(n) if index is None else np.asarray(index, np.int64)
+        if len(self.index) and (self.index.min() < 0 or self.index.max() >= n):
+            raise ValueError("AnnotationArchive %s: index outside its %d frames" % (path, n))
+        self.imList = torch.zeros(len(self.index), 3, dtype=torch.long)
+        self.imList[:, 0] = torch.from_numpy(self.index)
+        self.imList[:, 2] = dataset_id
+
+    def __len__(self):
+        return len(self.index)
+
+    def __getitem__(self, i):
+        k = int(self.index[i])
+        img = np.ascontiguousarray(self.a["Images"][k], dtype=np.uint8)
+        pc, pupil, iris = self.pupil_loc[k], self.fits_pupil[k], self.fits_iris[k]
+        # (the label is painted on the device: "mask all 0" is decided there, device_batch)
+        return (img, self.records[k], np.stack([iris, pupil]), pc, read_cond(pc, np.ones(1), pupil, iris), self.imList[i].numpy().copy())
+
+
+def open_archive(path, index=None, dataset_id=0):
+    """RawArchive or AnnotationArchive, by the array names of the file."""
+    with np.load(path) as z:
+        annotated = "ann_ball" in z.files
+    return (AnnotationArchive if annotated else RawArchive)(path, index, dataset_id)
+
+
+def collate_for(dataset):
+    """The ``collate_fn`` that fits a raw Dataset: collate_annotated for an AnnotationArchive, collate_raw otherwise."""
+    return collate_annotated if isinstance(dataset, AnnotationArchive) else collate_raw
+
+
 def split_archive(path, every=10):
-    """(training set, validation set) of one archive for train.py: every ``every``-th frame validates, the rest train; an archive
-    of fewer frames than that serves both."""
-    n = len(RawArchive(path))
+    """(training set, validation set) of one archive (of either kind, open_archive) for train.py: every ``every``-th frame validates,
+    the rest train; an archive of fewer frames than that serves both."""
+    n = len(open_archive(path))
     idx = np.arange(n)
     if n < every:
-        return RawArchive(path), RawArchive(path)
-    return RawArchive(path, idx[idx % every != every - 1]), RawArchive(path, idx[idx % every == every - 1])
+        return open_archive(path), open_archive(path)
+    return open_archive(path, idx[idx % every != every - 1]), open_archive(path, idx[idx % every == every - 1])
 
 
 def collate_raw(samples):
@@ -127,6 +183,21 @@ def collate_raw(samples):
                     np.stack([np.asarray(s[3], np.float64) for s in samples]).reshape(B, 2),
                     np.stack([np.asarray(s[4], bool) for s in samples]).reshape(B, 4),
                     np.stack([np.asarray(s[5], np.int64) for s in samples]).reshape(B, 3))
+
+
+def collate_annotated(samples):
+    """A list of AnnotationArchive samples -> AnnotBatch."""
+    B = len(samples)
+    hw = np.array([s[0].shape for s in samples], np.int32).reshape(B, 2)
+    R, C = int(hw[:, 0].max()), int(hw[:, 1].max())
+    images = np.zeros((B, R, C), np.uint8)
+    for b, s in enumerate(samples):
+        images[b, :hw[b, 0], :hw[b, 1]] = s[0]
+    return AnnotBatch(images, np.stack([np.asarray(s[1], np.int32) for s in samples]).reshape(B, -1), hw,
+                      np.stack([np.asarray(s[2], np.float64) for s in samples]).reshape(B, 2, 5),
+                      np.stack([np.asarray(s[3], np.float64) for s in samples]).reshape(B, 2),
+                      np.stack([np.asarray(s[4], bool) for s in samples]).reshape(B, 4),
+                      np.stack([np.asarray(s[5], np.int64) for s in samples]).reshape(B, 3))
 
 
 def pad_offsets(src_hw, size):
@@ -231,7 +302,9 @@ def stage_geometry(elParam, pupil_center, src_hw, size, scale=False):
 
 def device_batch(raw, size=(240, 320), scale=False, augment=False, choices=None, on_cv2="device", host_noise=False, ellipse="given",
                  device=None):
-    """The reference's ``__getitem__`` (CurriculumLib.py:94-166) for a RawBatch, on the device.  Returns the nine tensors of :166
+    """The reference's ``__getitem__`` (CurriculumLib.py:94-166) for a RawBatch or an AnnotBatch, on the device.  For an AnnotBatch
+    the stored labels are painted on the device from the records (dataprep.labels_from_annotations, the Masks_noSkin map) in place of
+    an uploaded plane, and cond[:,1] ("mask all 0") is its status bit, composed on the device; everything else is the same path.  Returns the nine tensors of :166
     with a leading batch axis, all on the GPU: img float32 [B,1,H,W], label int64 [B,H,W], spatialWeights float32 [B,H,W], distMap
     float32 [B,3,H,W], pupil_center and iris_center float32 [B,2], elNorm float32 [B,2,5], cond bool [B,4], imInfo int64 [B,3].
 
@@ -249,7 +322,14 @@ def device_batch(raw, size=(240, 320), scale=False, augment=False, choices=None,
     size = (int(size[0]), int(size[1]))
     el, pc = stage_geometry(raw.elParam, raw.pupil_center, raw.src_hw, size, scale)       # refuses frames that do not fit, first
     dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
-    img, lab = stage(torch.from_numpy(raw.images).to(dev), torch.from_numpy(raw.labels).to(dev), raw.src_hw, size, scale)
+    annotated = isinstance(raw, AnnotBatch)
+    images = torch.from_numpy(raw.images).to(dev)
+    if annotated:
+        labels, status = dataprep.labels_from_annotations(raw.records, raw.images.shape[1:], raw.src_hw, with_skin=False, return_status=True,
+                                                          device=dev)
+    else:
+        labels = torch.from_numpy(raw.labels).to(dev)
+    img, lab = stage(images, labels, raw.src_hw, size, scale)
     if augment:
         img, lab, pc, el, _ = data_augment.augment_batch(img, lab, pc, el, choices, host_noise=host_noise, on_cv2=on_cv2)
     x, lab = finish(img, lab)
@@ -261,6 +341,8 @@ def device_batch(raw, size=(240, 320), scale=False, augment=False, choices=None,
         return x, lab, sw, dm, pc_d, ic_d, eln, cond.bool(), info
     H, W = lab.shape[1:]
     cond = torch.from_numpy(np.ascontiguousarray(raw.cond, dtype=bool)).to(dev)
+    if annotated:
+        cond[:, 1] = (status & dataprep.ANNOT_EMPTY) != 0
     el, pc = el.to(dev), pc.to(dev)
     gone = cond[:, [3, 2]][..., None]                         # iris first: cond[3] is the iris ellipse, cond[2] the pupil's
     eln = torch.where(gone, -torch.ones_like(el), dataprep._ellipse_info(torch.where(gone, torch.ones_like(el), el), H, W))

@@ -130,7 +130,9 @@ def calc_acc(args, testloader, model, edge_model, device):
             break
         if args.device_loader:                 # a RawBatch: the nine tensors are built on the GPU (egne_amd.loader), no augmentation
             from egne_amd import loader
-            batch = loader.device_batch(batch, augment=False)
+            from egne_amd.args import loader_geometry
+            size, scale = loader_geometry(args)
+            batch = loader.device_batch(batch, size=size, scale=scale, augment=False)
         waiting.append(batch)
         r = pipe.submit(batch[0].to(device), second(batch))
         if r is not None:
@@ -204,7 +206,8 @@ def main(argv=None):
         from egne_amd.bdcn_new import BDCN
         from egne_amd.modelSummary import get_model
         if args.device_loader:
-            testObj = loader.RawArchive(args.raw_archive)
+            testObj = loader.open_archive(args.raw_archive)
+            collate = loader.collate_for(testObj)
         else:
             with open(os.path.join(args.path2data, 'baseline', 'cond_' + args.curObj + '.pkl'), 'rb') as f:
                 _, _, testObj = pickle.load(f)                     # test.py:271-274

@@ -58,7 +58,9 @@ def lossandaccuracy(args, loader, model, edge_model, alpha, device, ledger=None)
                 break
             if args.device_loader:      # a RawBatch (egne_amd.loader): no augmentation for validation
                 from egne_amd import loader
-                batch = loader.device_batch(batch, augment=False)
+                from egne_amd.args import loader_geometry
+                size, scale = loader_geometry(args)
+                batch = loader.device_batch(batch, size=size, scale=scale, augment=False)
             img, labels, sw, dm, pc, ic, eln, cond, imInfo = batch
             for attempt in (0, 1, 2):
                 with torch.no_grad():
@@ -122,7 +124,9 @@ def main(argv=None):
     if args.device_loader:
         # raw samples from the Dataset, the item path of CurriculumLib.py:94-166 per batch on the GPU (egne_amd.loader.device_batch)
         from egne_amd import loader
+        from egne_amd.args import loader_geometry
         collate = loader.collate_raw
+        loader_size, loader_scale = loader_geometry(args)
     if args.synthetic:
         Eyes = loader.SyntheticRawEyes if args.device_loader else _entry.SyntheticEyes
         trainObj = Eyes(args.synthetic, seed=1234)   # same set on every rank; the sampler below shards it
@@ -133,6 +137,7 @@ def main(argv=None):
         from egne_amd.modelSummary import get_model
         if args.device_loader:
             trainObj, validObj = loader.split_archive(args.raw_archive)
+            collate = loader.collate_for(trainObj)
         else:
             with open(os.path.join(args.path2data, 'baseline', 'cond_' + args.curObj + '.pkl'), 'rb') as f:
                 trainObj, validObj, _ = pickle.load(f)            # train.py:86-92
@@ -208,7 +213,7 @@ def main(argv=None):
             if (args.overfit and bt >= args.overfit) or (args.test_normal and bt > 20):
                 break
             if args.device_loader:      # a RawBatch: the nine tensors are built on the GPU, augmented as CurriculumLib.py:114 does for training
-                batch = loader.device_batch(batch, augment=True, on_cv2="device")
+                batch = loader.device_batch(batch, size=loader_size, scale=loader_scale, augment=True, on_cv2="device")
             img, labels, sw, dm, pc, ic, eln, cond, imInfo = batch
 
             def rest(edge, img=img, labels=labels, sw=sw, dm=dm, pc=pc, ic=ic, eln=eln, cond=cond, imInfo=imInfo, bt=bt):

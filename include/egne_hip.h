@@ -1303,6 +1303,47 @@ int egne_disp_grid(const void* img, const void* mask, const void* el, const void
                    int override_, int draw_gt, int count, int nrow, const void* cos_sin, void* grid, void* bgr_u8, void* status,
                    void* workspace, void* stream);
 
+/* ---- label maps from TEyeD annotations (csrc/annot.hip, egne_amd.dataprep.labels_from_annotations) -----------------------------
+ * What the reference's dataset_generation/Extract_TEyeD_*_histo.py scripts draw per kept frame: Masks_noSkin = zeros, cv2.circle
+ * (eyeball) -> 1, cv2.ellipse (iris) -> 2, cv2.ellipse (pupil) -> 3; Masks = the same map, zeroed outside cv2.fillPoly of the 34
+ * eyelid landmarks.  The ARGUMENTS handed to OpenCV are pinned by the reference (tests/golden/annot.npz) and applied on the host
+ * by dataprep.pack_annotations; the PIXELS are this project's rules below, not OpenCV's (its boundary pixels are unpinned).  The call
+ * queues three launches on `stream`, synchronises nothing and can be captured in a graph; its only atomic is an integer atomicOr
+ * on the status word.
+ *
+ * records: B records of EGNE_ANNOT_RECORD_WORDS 32-bit words, 8-byte aligned (csrc/annot_core.h):
+ *   word 0 flags (EGNE_ANNOT_HAS_*: an absent shape is skipped); word 1 n, the lid's vertices, 0 .. 64; words 2..4 ball bx, by, br;
+ *   word 5 zero; words 6..9 iris ex, ey, A, B, words 10..13 its c, s as two float64 (cos and sin of the angle, made by the host: the
+ *   device calls no trigonometry); words 14..21 the pupil likewise; words 22.. the lid's x, y pairs.  Every integer is at most 2^20
+ *   in magnitude (pack_annotations refuses more), so that no int64 product overflows.
+ * src_hw int32 [B,2] or null: the frame's own (rows, columns) inside the canvas, clamped to it; pixels at or beyond them stay 0 (the
+ *   RawBatch layout).  noskin, skin (or null): int8 [B,R,C]; status int32 [B].  B <= 65535; R, C <= 2^20.
+ *
+ * Pixel (x, y), x the column:
+ *   circle: dx * dx + dy * dy <= br * br in int64 (dx = x - bx, dy = y - by); br == 0 is the centre pixel.
+ *   ellipse: X = dx * c + dy * s, Y = dy * c - dx * s (cv2.ellipse's convention: the first axis along (c, s), y down); the pixel
+ *     belongs iff (X * B) * (X * B) + (Y * A) * (Y * A) <= (A * B) * (A * B) in float64, every operation rounded on its own in this
+ *     order (no contraction).  Evaluated inside |dx|, |dy| <= max(A, B) + 1 only; with c * c + s * s = 1 to within rounding no pixel
+ *     outside that square satisfies it.  A half-axis of zero (or below) paints nothing and sets a status bit -- OpenCV would draw a
+ *     line segment there.
+ *   polygon (closed, n vertices): even-odd with the boundary included.  Every edge with y0 != y1, oriented so that y0 < y1, toggles
+ *     the parity of a pixel with y0 <= y < y1 and (x - x0) * (y1 - y0) - (x1 - x0) * (y - y0) < 0 in int64; a pixel with a zero cross
+ *     product inside an edge's bounding box belongs regardless of parity (horizontal edges, zero-area polygons).  Self-intersections
+ *     and repeated vertices need no special case.
+ *   noskin = 0, then ball -> 1, iris -> 2, pupil -> 3; skin = noskin where the lid polygon holds, else 0; without the lid skin = noskin.
+ * status[b]: EGNE_ANNOT_IRIS_ZERO_AXIS / EGNE_ANNOT_PUPIL_ZERO_AXIS: that ellipse is present with a half-axis <= 0;
+ *   EGNE_ANNOT_EMPTY: no pixel of the frame's noskin map carries a class (readImage's "mask all 0", cond[1] of the batch). */
+#define EGNE_ANNOT_RECORD_WORDS 150
+#define EGNE_ANNOT_HAS_BALL 1
+#define EGNE_ANNOT_HAS_IRIS 2
+#define EGNE_ANNOT_HAS_PUPIL 4
+#define EGNE_ANNOT_HAS_LID 8
+#define EGNE_ANNOT_IRIS_ZERO_AXIS 1
+#define EGNE_ANNOT_PUPIL_ZERO_AXIS 2
+#define EGNE_ANNOT_EMPTY 4
+int egne_labels_from_annotations(const void* records, const int* src_hw, int B, int R, int C, int8_t* noskin, int8_t* skin, int* status,
+                                 void* stream);
+
 const char* egne_last_error(void);
 int egne_version(void);
 int egne_sizeof(int which);   /* 0 egne_conv_desc, 1 egne_loss_desc, 2 egne_bdcn_tail_desc, 3 egne_dst, 4 egne_conv_query, 5 egne_conv_choice */
