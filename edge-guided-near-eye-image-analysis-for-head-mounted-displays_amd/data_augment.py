@@ -37,6 +37,7 @@ import torch
 
 from . import _lib
 from .engine import require_cuda
+from .frame_io import device_table
 
 CV2_CHOICES = (1, 5, 6)
 GAMMAS = (0.6, 0.8, 1.2, 1.4)
@@ -52,7 +53,7 @@ MAX_LINES = 9            # np.random.randint(1, 10)
 LINE_RADIUS2 = 4.0       # thickness 4: a capsule of radius 2 (squared)
 LINE_MARGIN = 4          # segments are clipped to [-4, W+3] x [-4, H+3]: nothing outside it reaches a pixel of the frame
 INTER_BITS = 5           # OpenCV's interpolation tables hold 32 phases per pixel
-_HOST_TABLES, _DEVICE_TABLES = {}, {}
+_HOST_TABLES = {}
 
 
 def gaussian_q8(sigma):
@@ -80,7 +81,7 @@ def gaussian_q8_tables():
 
 def lanczos4_phase_table():
     """The 1-D weights of the 8 Lanczos (a = 4) taps at -3..+4 around a source position for each of the 32 sub-pixel phases (float64
-    [32,8], rows normalised): the expression of evaluate.resize_lanczos4 / lanczos4_table at frac = phase / 32."""
+    [32,8], rows normalised): the expression of frame_io.lanczos4_table at frac = phase / 32."""
     if "lanczos" not in _HOST_TABLES:
         frac = np.arange(1 << INTER_BITS) / float(1 << INTER_BITS)
         taps = np.arange(-3, 5)
@@ -244,14 +245,6 @@ def draw(B, shape, choices=None, host_noise=False, on_cv2="raise", cv2_params=No
     return choice, param, lut, noise
 
 
-def _device_table(key, device, make):
-    """Small constant tables of the OpenCV branches, uploaded once per device (as evaluate._device_table)."""
-    k = (key, str(device))
-    if k not in _DEVICE_TABLES:
-        _DEVICE_TABLES[k] = tuple(torch.from_numpy(a).to(device) for a in make())
-    return _DEVICE_TABLES[k]
-
-
 def augment_cv(img, label, oimg, olabel, choice, cv):
     """The second launch (csrc/augment_cv.hip): rewrites the frames of ``oimg`` / ``olabel`` (which hold egne_augment's copy) whose
     ``choice`` is 1, 5 or 6 from ``img`` / ``label``; ``cv`` as draw() fills it (NumPy arrays of B rows)."""
@@ -262,7 +255,7 @@ def augment_cv(img, label, oimg, olabel, choice, cv):
     frame_d = torch.from_numpy(frame).to(dev)
     segs_d = torch.from_numpy(np.ascontiguousarray(cv["segs"], dtype=np.float64)).to(dev)
     rot_d = torch.from_numpy(np.ascontiguousarray(cv["rot"], dtype=np.float64)).to(dev)
-    q8_d, phase_d = _device_table("augment_cv", dev, lambda: (gaussian_q8_tables(), lanczos4_phase_table()))
+    q8_d, phase_d = device_table("augment_cv", dev, lambda: (gaussian_q8_tables(), lanczos4_phase_table()))
     _lib.check(_lib.lib().egne_augment_cv(img.data_ptr(), label.data_ptr(), frame_d.data_ptr(), frame.ctypes.data, segs_d.data_ptr(),
                                           rot_d.data_ptr(), q8_d.data_ptr(), phase_d.data_ptr(), oimg.data_ptr(), olabel.data_ptr(),
                                           B, H, W, _lib.stream_ptr()), "augment_cv")

@@ -9,7 +9,7 @@ Which pixels are the reference's: the uint8 image handed to equalizeHist, both n
 the paints, the clip of the outlines to [6, size - 6], min(count, B), the cond / override rule and the integers handed to
 ellipse_perimeter (tests/golden/dispgrid.npz records them from the reference's own function).  Which are this project's rules, because
 OpenCV, scikit-image and torchvision do the rest there: the equalisation (OpenCV's published rule), the outline pixels
-(evaluate._draw_ellipse's 720 samples, not scikit-image's perimeter), the grid layout (make_grid's documented one) and the uint8 form.
+(frame_io._draw_ellipse's 720 samples, not scikit-image's perimeter), the grid layout (make_grid's documented one) and the uint8 form.
 include/egne_hip.h states all of them.
 """
 import torch
@@ -45,7 +45,7 @@ def image_grid(img, mask, el, pupil_center=None, cond=None, el_gt=None, heatmaps
     outlines, in the colour of the reference's commented-out lines.  Returns the float32 grid [3,Hg,Wg]; with ``return_u8`` also the
     uint8 BGR image [Hg,Wg,3] (rint(255 * clip(grid, 0, 1)): how imshow shows the grid), with ``return_status`` also the int32 status
     word of every drawn frame (STATUS_* bits).  Queues on the current stream, synchronises nothing, can be captured in a graph."""
-    from egne_amd import _lib, evaluate
+    from egne_amd import _lib, frame_io
     if torch.is_tensor(img) and img.dim() == 4 and img.shape[1] == 1:
         img = img[:, 0]
     _check(img, "img", torch.float32, (None, None, None))
@@ -71,7 +71,7 @@ def image_grid(img, mask, el, pupil_center=None, cond=None, el_gt=None, heatmaps
     el_gt = None if el_gt is None else el_gt[:n].contiguous()
     cond = None if cond is None else cond[:n].contiguous()
     dev = img.device
-    cs, = evaluate._device_table("outline", dev, evaluate._outline_table)
+    cs, = frame_io.device_table("outline", dev, frame_io.outline_table)
     Hg, Wg = grid_shape(n, nrow, H, W)
     L = _lib.lib()
     grid = torch.empty((3, Hg, Wg), dtype=torch.float32, device=dev)
@@ -107,10 +107,10 @@ def script_grid(model_name, img, mask, el_flat, cond, el_gt, override):
 
 def save_grid(path, grid_u8, quality=90):
     """Write the uint8 BGR image of image_grid(..., return_u8=True) as a baseline JPEG file, encoded on the device
-    (evaluate.encode_jpeg_device).  Synchronises: the file's bytes come down here."""
-    from egne_amd import evaluate
+    (mjpeg.encode_jpeg_device).  Synchronises: the file's bytes come down here."""
+    from egne_amd import mjpeg
     _check(grid_u8, "grid_u8", torch.uint8, (None, None, 3))
-    out, lengths, flags = evaluate.encode_jpeg_device(grid_u8[None], quality=quality)
+    out, lengths, flags = mjpeg.encode_jpeg_device(grid_u8[None], quality=quality)
     length, flag = int(lengths[0].item()), int(flags[0].item())
     if flag or length <= 0:
         raise RuntimeError("save_grid: the JPEG file of a %dx%d grid did not fit its slot" % (grid_u8.shape[0], grid_u8.shape[1]))

@@ -19,7 +19,7 @@ An archive may hold the TEyeD ANNOTATIONS instead of label planes (AnnotationArc
 either kind): ``collate_annotated`` then stacks an AnnotBatch, whose ~0.6 KB record per frame is uploaded in place of the int8 plane,
 and ``device_batch`` paints the labels on the device (dataprep.labels_from_annotations) in front of the same five stages.
 
-PARITY: the Lanczos resize of ``scale`` is evaluate.resize_lanczos4 (same device code as the evaluate.py front end), whose parity
+PARITY: the Lanczos resize of ``scale`` is frame_io.resize_lanczos4 (same device code as the evaluate.py front end), whose parity
 with cv2.resize is UNPINNED (OpenCV quantises the tap weights, this float64 restatement does not); the nearest-neighbour label resize
 and everything else of the stage are exact.  spatial_weights and the cv2 branches of the augmentation carry their own notes.
 """
@@ -221,9 +221,9 @@ def stage(images, labels, src_hw, size=(240, 320), scale=False):
     """pad2Size and the optional scaleFn for a batch, one launch (egne_loader_stage).  ``images`` uint8 and ``labels`` int8
     [B,Rmax,Cmax] on the device (RawBatch layout), ``src_hw`` [B,2] on the HOST (checked here, before the launch).  Returns the uint8
     image and the int64 label [B,Hs,Ws]: what data_augment.augment_batch takes.  With ``scale`` the image is
-    evaluate.resize_lanczos4 of the padded canvas, byte for byte (PARITY WITH cv2.resize UNPINNED, as for resize_lanczos4 itself),
-    the label evaluate.resize_nearest."""
-    from . import evaluate
+    frame_io.resize_lanczos4 of the padded canvas, byte for byte (PARITY WITH cv2.resize UNPINNED, as for resize_lanczos4 itself),
+    the label frame_io.resize_nearest."""
+    from . import frame_io
     require_cuda(images, "images")
     require_cuda(labels, "labels")
     if images.dtype != torch.uint8 or images.dim() != 3 or labels.dtype != torch.int8 or labels.shape != images.shape:
@@ -242,11 +242,11 @@ def stage(images, labels, src_hw, size=(240, 320), scale=False):
     none = (None, None)
     rows = cols = near = none
     if (Hs, Ws) != (H, W):
-        table = evaluate._device_table
-        rows = table(("lanczos", H, Hs), dev, lambda: evaluate.lanczos4_table(H, Hs)) if Hs != H else none
-        cols = table(("lanczos", W, Ws), dev, lambda: evaluate.lanczos4_table(W, Ws)) if Ws != W else none
-        near = table(("nearest", H, Hs, W, Ws), dev, lambda: (evaluate.nearest_table(H, Hs).astype(np.int32),
-                                                              evaluate.nearest_table(W, Ws).astype(np.int32)))
+        table = frame_io.device_table
+        rows = table(("lanczos", H, Hs), dev, lambda: frame_io.lanczos4_table(H, Hs)) if Hs != H else none
+        cols = table(("lanczos", W, Ws), dev, lambda: frame_io.lanczos4_table(W, Ws)) if Ws != W else none
+        near = table(("nearest", H, Hs, W, Ws), dev, lambda: (frame_io.nearest_table(H, Hs).astype(np.int32),
+                                                              frame_io.nearest_table(W, Ws).astype(np.int32)))
     hw_d = torch.from_numpy(hw).to(dev)
     oimg = torch.empty((B, Hs, Ws), dtype=torch.uint8, device=dev)
     olab = torch.empty((B, Hs, Ws), dtype=torch.int64, device=dev)

@@ -5,7 +5,7 @@
 
 The job of the reference's dataset_generation/Extract_TEyeD_{LPW,NvGaze_AR}_histo.py, without their H5 / deepdish output:
 
-    frames        a Motion-JPEG .avi (evaluate.mjpeg_frames; any other codec is refused: TEyeD's H.264 .mp4 files cannot be decoded
+    frames        a Motion-JPEG .avi (mjpeg.mjpeg_frames; any other codec is refused: TEyeD's H.264 .mp4 files cannot be decoded
                   here and have to be transcoded or extracted first), or a directory of images read through PIL .convert('L') in the
                   order of their sorted names, as the NvGaze script reads them
     annotations   PREFIXiris_eli.txt, PREFIXpupil_eli.txt, PREFIXeye_ball.txt, PREFIXlid_lm_2D.txt: ';'-separated floats, the first
@@ -84,7 +84,7 @@ def iter_frames(path):
     if codec != b"MJPG":
         raise SystemExit("make_archive: %s is not a Motion-JPEG .avi (%s): only Motion-JPEG can be decoded here; transcode the video to "
                          "MJPEG or extract its frames into a directory" % (path, "codec %r" % codec.decode("latin1") if codec else "no AVI video stream"))
-    from .evaluate import mjpeg_frames
+    from .mjpeg import mjpeg_frames
     for frame in mjpeg_frames(path):
         yield lambda frame=frame: frame
 

@@ -5,6 +5,7 @@ import pytest
 import torch
 
 import cleanup_refs as R
+import video_harness as V
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -198,50 +199,24 @@ def test_downstream_fit_reads_the_cleaned_map(seed_kind):
 
 
 # ---- script level --------------------------------------------------------------------------------------------------------------------
-def _clip(tmp_path):
-    from common import gold
-    from egne_amd import evaluate as E
-    g = gold("evaluate_real_frames")
-    vid = tmp_path / "clip.avi"
-    w = E.MJPEGWriter(str(vid), 30, (640, 240))
-    for k in range(2):
-        fr = np.concatenate([g["eyes"][2 * k], g["eyes"][2 * k + 1]], axis=1)
-        for _ in range(2):
-            w.write(np.stack([fr] * 3, axis=2))
-    w.release()
-    return vid
-
-
-def _video(E, vid, tmp_path, nets, monkeypatch, extra, method):
-    """evaluate_ellseg_per_video with --clean_mask 1 -> (ellipse dictionary, the frames handed to the two video writers, how many
-    times the clean-up stage was called)."""
+def _video(vid, tmp_path, nets, monkeypatch, extra, method):
+    """evaluate_ellseg_per_video with --clean_mask 1 -> (ellipse dictionary, equal to the one on disk, the frames handed to the two
+    video writers, how many times the clean-up stage was called)."""
     import egne_amd.utils as U
-    bd, net = nets
-    written, calls = [], []
-    real_write, real_clean = E.MJPEGWriter.write, U.clean_class_maps
-
-    def write(self, frame):
-        written.append((self.path.rsplit("_", 2)[-2], np.array(frame, copy=True)))
-        return real_write(self, frame)
+    calls, real_clean = [], U.clean_class_maps
 
     def clean(mask, layers, *a, **k):
         calls.append(layers)
         return real_clean(mask, layers, *a, **k)
-    monkeypatch.setattr(E.MJPEGWriter, "write", write)
     monkeypatch.setattr(U, "clean_class_maps", clean)
-    args = E.parse_args(["--path2data", str(tmp_path), "--method", method, "--clean_mask", "1"] + extra)
-    res = E.evaluate_ellseg_per_video(str(vid), args, net, bd, torch.device(DEV))
+    r = V.run(vid, tmp_path, nets, ["--clean_mask", "1"] + extra, method)
     monkeypatch.undo()
-    on_disk = np.load(str(tmp_path / ("clip_pred2_%s.npy" % method)), allow_pickle=True).item()
-    assert set(on_disk) == set(res) and all(np.array_equal(on_disk[k], res[k], equal_nan=True) for k in res)
-    return res, written, calls
+    V.same_ellipses(r.files[0], r.res, equal_nan=True)
+    return r.res, r.written, calls
 
 
-def _equal(res_a, res_b, what):
-    assert set(res_a) == set(res_b)
-    for k in res_a:
-        for e_a, e_b in zip(res_a[k], res_b[k]):
-            assert e_a.shape == (5,) and np.array_equal(e_a, e_b, equal_nan=True), (what, k, e_a, e_b)
+def _equal(res_a, res_b):
+    V.same_ellipses(res_a, res_b, equal_nan=True)
 
 
 @pytest.mark.parametrize("seed", ["pred", "mask"])
@@ -249,25 +224,24 @@ def test_video_clean_mask_same_results_through_every_path(tmp_path, nets, monkey
     """--clean_mask 1 on the clip of test_evaluate_video_end_to_end: the batched loop, --low_latency 1 and --device_io 1 --low_latency 1
     (the stage inside the captured graph) write the same ellipses; --device_io 0 and 1 hand byte-identical frames to both video
     writers.  A first run calibrates the plans."""
-    from egne_amd import evaluate as E
     from egne_amd.utils import DEFAULT_CLEAN_LAYERS
-    vid = _clip(tmp_path)
+    vid = V.clip(tmp_path)
     extra = ["--ellipse_seed", seed]
-    _video(E, vid, tmp_path, nets, monkeypatch, extra, "warm")
-    host, wr_h, calls_h = _video(E, vid, tmp_path, nets, monkeypatch, extra, "host")
-    dev, wr_d, calls_d = _video(E, vid, tmp_path, nets, monkeypatch, extra + ["--device_io", "1"], "dev")
-    live, wr_lh, calls_l = _video(E, vid, tmp_path, nets, monkeypatch, extra + ["--low_latency", "1"], "live")
-    live_io, wr_l, calls_lio = _video(E, vid, tmp_path, nets, monkeypatch, extra + ["--device_io", "1", "--low_latency", "1"], "liveio")
+    _video(vid, tmp_path, nets, monkeypatch, extra, "warm")
+    host, wr_h, calls_h = _video(vid, tmp_path, nets, monkeypatch, extra, "host")
+    dev, wr_d, calls_d = _video(vid, tmp_path, nets, monkeypatch, extra + ["--device_io", "1"], "dev")
+    live, wr_lh, calls_l = _video(vid, tmp_path, nets, monkeypatch, extra + ["--low_latency", "1"], "live")
+    live_io, wr_l, calls_lio = _video(vid, tmp_path, nets, monkeypatch, extra + ["--device_io", "1", "--low_latency", "1"], "liveio")
     assert set(k for k in host if isinstance(k, int)) == {0, 1, 2, 3} and all((j, i) in host for j in range(4) for i in range(2))
     for calls in (calls_h, calls_d, calls_l, calls_lio):
         assert calls and all(c == DEFAULT_CLEAN_LAYERS for c in calls)
-    _equal(host, dev, "batched vs device_io")
-    _equal(live, live_io, "low_latency vs device_io + low_latency")
+    _equal(host, dev)
+    _equal(live, live_io)
     if seed == "mask":
         # seeds from the (integer) cleaned map: the batch size cannot show.  The regression head's float seeds differ in their last
         # bits between a batch of eight and a batch of two, with or without the clean-up, so 'pred' is compared at equal batching only
-        _equal(host, live, "batched vs low_latency")
-        _equal(host, live_io, "batched vs device_io + low_latency")
+        _equal(host, live)
+        _equal(host, live_io)
     for wr_0, wr in ((wr_h, wr_d), (wr_lh, wr_l)):          # --device_io 0 against 1, in the batched loop and under --low_latency 1
         assert [w[0] for w in wr_0] == [w[0] for w in wr] and len(wr) == 8
         for (kind, fa), (_, fb) in zip(wr_0, wr):

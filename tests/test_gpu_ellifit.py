@@ -354,32 +354,31 @@ def test_fit_from_mask_with_ransac_seeds(fx):
         fit_ellipses_from_mask(m, seed_kind="canny")
 
 
-def test_video_ransac_seed_same_ellipses_and_frames_through_three_paths(tmp_path, nets, monkeypatch):
+def test_video_ransac_seed_same_ellipses_and_frames_through_three_paths(tmp_path, nets):
     """--ellipse_seed ransac on the clip of tests/test_gpu_mask_seed.py: the host path, --device_io 1 and --device_io 1 --low_latency 1
     (the whole estimator inside the captured graph) write the same ellipses; what they write is neither what pred nor what mask
     writes.  The frames handed to both video writers are byte-identical between --device_io 0 and 1 at the same --low_latency, as
     tests/test_gpu_evalio.py has it for pred: the edge network's map itself differs in a few bytes between a batch of the whole clip
     and a frame pair, whatever the seeds are."""
-    from egne_amd import evaluate as E
-    from test_gpu_evalio import _clip, _run, _same
-    vid = _clip(tmp_path)
+    import video_harness as V
+    vid = V.clip(tmp_path)
     flag = ["--ellipse_seed", "ransac"]
-    _run(E, vid, tmp_path, nets, monkeypatch, flag, "warm")
-    host, wr_h, _, _ = _run(E, vid, tmp_path, nets, monkeypatch, flag, "host")
-    dev, wr_d, _, _ = _run(E, vid, tmp_path, nets, monkeypatch, flag + ["--device_io", "1"], "dev")
-    host1, wr_h1, _, _ = _run(E, vid, tmp_path, nets, monkeypatch, flag + ["--low_latency", "1"], "host1")
-    live, wr_l, _, _ = _run(E, vid, tmp_path, nets, monkeypatch, flag + ["--device_io", "1", "--low_latency", "1"], "live")
-    assert all((j, i) in host for j in range(4) for i in range(2))
-    _same(host, wr_h, dev, wr_d)
-    _same(host1, wr_h1, live, wr_l)
-    assert set(host) == set(live)
-    for k in host:
-        for e_a, e_b in zip(host[k], live[k]):
+    V.run(vid, tmp_path, nets, flag, "warm")
+    host = V.run(vid, tmp_path, nets, flag, "host")
+    dev = V.run(vid, tmp_path, nets, flag + ["--device_io", "1"], "dev")
+    host1 = V.run(vid, tmp_path, nets, flag + ["--low_latency", "1"], "host1")
+    live = V.run(vid, tmp_path, nets, flag + ["--device_io", "1", "--low_latency", "1"], "live")
+    assert all((j, i) in host.res for j in range(4) for i in range(2))
+    V.same_frames(host, dev)
+    V.same_frames(host1, live)
+    assert set(host.res) == set(live.res)
+    for k in host.res:
+        for e_a, e_b in zip(host.res[k], live.res[k]):
             assert np.array_equal(e_a, e_b), (k, e_a, e_b)
     for other in ("pred", "mask"):
-        res, _, _, _ = _run(E, vid, tmp_path, nets, monkeypatch, ["--ellipse_seed", other], other)
-        assert any(not np.array_equal(host[k][0], res[k][0], equal_nan=True) or not np.array_equal(host[k][1], res[k][1], equal_nan=True)
-                   for k in host), other
+        res = V.run(vid, tmp_path, nets, ["--ellipse_seed", other], other).res
+        assert any(not np.array_equal(host.res[k][0], res[k][0], equal_nan=True) or not np.array_equal(host.res[k][1], res[k][1], equal_nan=True)
+                   for k in host.res), other
 
 
 @pytest.mark.parametrize("model", ["ritnet_v2", "deepvog"])

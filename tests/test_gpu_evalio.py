@@ -5,6 +5,7 @@ import numpy as np
 import pytest
 import torch
 
+import video_harness as V
 from evalio_cases import (OP_SHAPE, handmade_maps, host_render, host_u8, native_frames, near_half, outline_ties, resize_cases)
 
 pytestmark = pytest.mark.gpu
@@ -149,86 +150,29 @@ def test_render_network_outputs(case, nets):
     _render_and_compare(E, frames, eyes, ew, np.ascontiguousarray(edge), np.ascontiguousarray(seg), fit, ss, case + " (network outputs)")
 
 
-def _clip(tmp_path):
-    from common import gold
-    from egne_amd import evaluate as E
-    g = gold("evaluate_real_frames")
-    vid = tmp_path / "clip.avi"
-    w = E.MJPEGWriter(str(vid), 30, (640, 240))
-    for k in range(2):
-        fr = np.concatenate([g["eyes"][2 * k], g["eyes"][2 * k + 1]], axis=1)
-        for _ in range(2):
-            w.write(np.stack([fr] * 3, axis=2))
-    w.release()
-    return vid
-
-
-def _run(E, vid, tmp_path, nets, monkeypatch, extra, method):
-    """evaluate_ellseg_per_video with every frame handed to the two MJPEGWriters captured (before JPEG) and every transfer of the
-    device-I/O path recorded."""
-    bd, net = nets
-    written, up, down = [], [], []
-    real_write, real_up, real_down = E.MJPEGWriter.write, E._upload_u8, E._download
-
-    def write(self, frame):
-        written.append((self.path.rsplit("_", 2)[-2], np.array(frame, copy=True)))
-        return real_write(self, frame)
-
-    def upload(frames, device):
-        t = real_up(frames, device)
-        up.append((t.dtype, tuple(t.shape)))
-        return t
-
-    def download(t):
-        down.append((t.dtype, tuple(t.shape)))
-        return real_down(t)
-    monkeypatch.setattr(E.MJPEGWriter, "write", write)
-    monkeypatch.setattr(E, "_upload_u8", upload)
-    monkeypatch.setattr(E, "_download", download)
-    args = E.parse_args(["--path2data", str(tmp_path), "--method", method] + extra)
-    res = E.evaluate_ellseg_per_video(str(vid), args, net, bd, torch.device(DEV))
-    on_disk = np.load(str(tmp_path / ("clip_pred2_%s.npy" % method)), allow_pickle=True).item()
-    assert set(on_disk) == set(res)
-    monkeypatch.undo()
-    return res, written, up, down
-
-
-def _same(res_a, wr_a, res_b, wr_b):
-    assert set(res_a) == set(res_b)
-    for k in res_a:
-        for e_a, e_b in zip(res_a[k], res_b[k]):
-            assert e_a.shape == (5,) and np.array_equal(e_a, e_b), (k, e_a, e_b)
-    assert [w[0] for w in wr_a] == [w[0] for w in wr_b] and len(wr_a) == 8
-    for (kind, fa), (_, fb) in zip(wr_a, wr_b):
-        assert fa.dtype == np.uint8 and fa.shape == fb.shape == (240, 640, 3)
-        assert np.array_equal(fa, fb), "%s frame differs in %d bytes" % (kind, np.count_nonzero(fa != fb))
-
-
 @pytest.mark.parametrize("live", ["0", "1"])
-def test_video_end_to_end_equals_the_host_path(tmp_path, nets, monkeypatch, live):
+def test_video_end_to_end_equals_the_host_path(tmp_path, nets, live):
     """The clip of test_evaluate_video_end_to_end with --device_io 1 against --device_io 0, same process, same plans: equal ellipse
     dictionaries, byte-identical frames into both video writers.  A first host-path run calibrates the plans, so both compared runs
     start from the same plan state."""
-    from egne_amd import evaluate as E
-    vid = _clip(tmp_path)
-    _run(E, vid, tmp_path, nets, monkeypatch, ["--low_latency", live], "warm")
-    res0, wr0, up0, down0 = _run(E, vid, tmp_path, nets, monkeypatch, ["--low_latency", live, "--device_io", "0"], "host")
-    res1, wr1, up1, down1 = _run(E, vid, tmp_path, nets, monkeypatch, ["--low_latency", live, "--device_io", "1"], "dev")
-    assert not up0 and not down0 and up1 and down1
-    assert set(k for k in res1 if isinstance(k, int)) == {0, 1, 2, 3} and all((j, i) in res1 for j in range(4) for i in range(2))
-    _same(res0, wr0, res1, wr1)
+    vid = V.clip(tmp_path)
+    V.run(vid, tmp_path, nets, ["--low_latency", live], "warm")
+    host = V.run(vid, tmp_path, nets, ["--low_latency", live, "--device_io", "0"], "host")
+    dev = V.run(vid, tmp_path, nets, ["--low_latency", live, "--device_io", "1"], "dev")
+    assert not host.up and not host.down and dev.up and dev.down
+    assert set(k for k in dev.res if isinstance(k, int)) == {0, 1, 2, 3} and all((j, i) in dev.res for j in range(4) for i in range(2))
+    V.same_frames(host, dev)
 
 
-def test_video_transfers_are_uint8_frames_and_ellipses_only(tmp_path, nets, monkeypatch):
+def test_video_transfers_are_uint8_frames_and_ellipses_only(tmp_path, nets):
     """--device_io 1 --low_latency 1: per frame pair one uint8 frame goes up; two uint8 BGR frames and 20 doubles per eye come down."""
-    from egne_amd import evaluate as E
-    vid = _clip(tmp_path)
-    _, _, up, down = _run(E, vid, tmp_path, nets, monkeypatch, ["--low_latency", "1", "--device_io", "1"], "dev")
-    assert up == [(torch.uint8, (1, 240, 640))] * 4
-    assert down == [(torch.uint8, (1, 240, 640, 3)), (torch.uint8, (1, 240, 640, 3)), (torch.float64, (2, 2, 5))] * 4
-    _, _, up, down = _run(E, vid, tmp_path, nets, monkeypatch, ["--low_latency", "0", "--device_io", "1"], "dev")
-    assert up == [(torch.uint8, (4, 240, 640))]
-    assert down == [(torch.uint8, (4, 240, 640, 3)), (torch.uint8, (4, 240, 640, 3)), (torch.float64, (8, 2, 5))]
+    vid = V.clip(tmp_path)
+    r = V.run(vid, tmp_path, nets, ["--low_latency", "1", "--device_io", "1"], "dev")
+    assert r.up == [(torch.uint8, (1, 240, 640))] * 4
+    assert r.down == [(torch.uint8, (1, 240, 640, 3)), (torch.uint8, (1, 240, 640, 3)), (torch.float64, (2, 2, 5))] * 4
+    r = V.run(vid, tmp_path, nets, ["--low_latency", "0", "--device_io", "1"], "dev")
+    assert r.up == [(torch.uint8, (4, 240, 640))]
+    assert r.down == [(torch.uint8, (4, 240, 640, 3)), (torch.uint8, (4, 240, 640, 3)), (torch.float64, (8, 2, 5))]
 
 
 @pytest.mark.parametrize("live", ["0", "1"])
@@ -236,17 +180,17 @@ def test_video_redo_after_a_reported_overflow(tmp_path, nets, monkeypatch, live)
     """The re-calibration paths with device I/O: the first overflow query of the run answers "overflowed", so the batch is run again
     from the retained uint8 device frames (eagerly / through a fresh capture) and rendered again -- with the same results."""
     from egne_amd import evaluate as E
-    vid = _clip(tmp_path)
-    res0, wr0, _, _ = _run(E, vid, tmp_path, nets, monkeypatch, ["--low_latency", live, "--device_io", "1"], "dev")
+    vid = V.clip(tmp_path)
+    want = V.run(vid, tmp_path, nets, ["--low_latency", live, "--device_io", "1"], "dev")
     real, calls = E._overflowed, []
 
     def once(net):
         calls.append(1)
         return True if len(calls) == 1 else real(net)
     monkeypatch.setattr(E, "_overflowed", once)
-    res1, wr1, _, down = _run(E, vid, tmp_path, nets, monkeypatch, ["--low_latency", live, "--device_io", "1"], "redo")
+    got = V.run(vid, tmp_path, nets, ["--low_latency", live, "--device_io", "1"], "redo")
     assert len(calls) > 2
-    _same(res0, wr0, res1, wr1)
+    V.same_frames(want, got)
 
 
 def test_argument_checks():

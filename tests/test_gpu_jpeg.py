@@ -8,6 +8,7 @@ import pytest
 import torch
 
 import jpeg_refs as J
+import video_harness as V
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -202,64 +203,19 @@ def test_stamp_numbers_equals_put_frame_number():
     assert np.array_equal(got, want) and not np.array_equal(got, frames)
 
 
-def _clip(tmp_path):
-    from common import gold
-    E = _E()
-    g = gold("evaluate_real_frames")
-    vid = tmp_path / "clip.avi"
-    w = E.MJPEGWriter(str(vid), 30, (640, 240))
-    for k in range(2):
-        fr = np.concatenate([g["eyes"][2 * k], g["eyes"][2 * k + 1]], axis=1)
-        for _ in range(2):
-            w.write(np.stack([fr] * 3, axis=2))
-    w.release()
-    return vid
-
-
-def _run(E, vid, tmp_path, nets, monkeypatch, extra, method):
-    """evaluate_ellseg_per_video with what reaches the two MJPEGWriters captured (frames before JPEG through write, finished streams
-    through write_jpeg) and every download of the device-I/O path recorded."""
-    bd, net = nets
-    written, streams, down = [], [], []
-    real_write, real_jpeg, real_down = E.MJPEGWriter.write, E.MJPEGWriter.write_jpeg, E._download
-
-    def write(self, frame):
-        written.append((self.path.rsplit("_", 2)[-2], np.array(frame, copy=True)))
-        return real_write(self, frame)
-
-    def write_jpeg(self, data):
-        streams.append((self.path.rsplit("_", 2)[-2], bytes(data)))
-        return real_jpeg(self, data)
-
-    def download(t):
-        down.append((t.dtype, tuple(t.shape)))
-        return real_down(t)
-    monkeypatch.setattr(E.MJPEGWriter, "write", write)
-    monkeypatch.setattr(E.MJPEGWriter, "write_jpeg", write_jpeg)
-    monkeypatch.setattr(E, "_download", download)
-    args = E.parse_args(["--path2data", str(tmp_path), "--method", method] + extra)
-    res = E.evaluate_ellseg_per_video(str(vid), args, net, bd, torch.device(DEV))
-    on_disk = np.load(str(tmp_path / ("clip_pred2_%s.npy" % method)), allow_pickle=True).item()
-    assert set(on_disk) == set(res)
-    monkeypatch.undo()
-    return res, written, streams, down
-
-
 @pytest.mark.parametrize("live", ["0", "1"])
-def test_video_end_to_end_equals_device_io(tmp_path, nets, monkeypatch, live):
+def test_video_end_to_end_equals_device_io(tmp_path, nets, live):
     """The clip of test_gpu_evalio with --device_io 1 --device_jpeg 1 against --device_io 1 after a warm-up run: equal ellipse
     dictionaries; every stream handed to write_jpeg is the restatement's encoding of the frame (frame number included) that the
     --device_io 1 run handed to write at the same position; only stream bytes, lengths / flags and ellipses come down."""
     E, R = _E(), _R()
-    vid = _clip(tmp_path)
+    vid = V.clip(tmp_path)
     base = ["--low_latency", live, "--device_io", "1"]
-    _run(E, vid, tmp_path, nets, monkeypatch, base, "warm")
-    res0, wr0, st0, down0 = _run(E, vid, tmp_path, nets, monkeypatch, base, "dev")
-    res1, wr1, st1, down1 = _run(E, vid, tmp_path, nets, monkeypatch, base + ["--device_jpeg", "1"], "jpg")
-    assert set(res0) == set(res1)
-    for k in res0:
-        for e_a, e_b in zip(res0[k], res1[k]):
-            assert e_a.shape == (5,) and np.array_equal(e_a, e_b), (k, e_a, e_b)
+    V.run(vid, tmp_path, nets, base, "warm")
+    dev = V.run(vid, tmp_path, nets, base, "dev")
+    jpg = V.run(vid, tmp_path, nets, base + ["--device_jpeg", "1"], "jpg")
+    V.same_ellipses(dev.res, jpg.res)
+    wr0, st0, wr1, st1, down1 = dev.written, dev.streams, jpg.written, jpg.streams, jpg.down
     assert len(wr0) == 8 and not st0 and not wr1
     assert [k for k, _ in st1] == [k for k, _ in wr0] and sorted(k for k, _ in st1) == ["edge"] * 4 + ["result"] * 4
     for pos, ((kind, frame), (_, stream)) in enumerate(zip(wr0, st1)):
@@ -284,36 +240,35 @@ def test_video_redo_after_a_reported_overflow(tmp_path, nets, monkeypatch, live)
     """The re-calibration path with --device_jpeg 1: the first overflow query answers "overflowed", the batch is rendered again and
     therefore encoded again -- same streams."""
     E = _E()
-    vid = _clip(tmp_path)
+    vid = V.clip(tmp_path)
     extra = ["--low_latency", live, "--device_io", "1", "--device_jpeg", "1"]
-    res0, wr0, st0, _ = _run(E, vid, tmp_path, nets, monkeypatch, extra, "jpg")
+    want = V.run(vid, tmp_path, nets, extra, "jpg")
     real, calls = E._overflowed, []
 
     def once(net):
         calls.append(1)
         return True if len(calls) == 1 else real(net)
     monkeypatch.setattr(E, "_overflowed", once)
-    res1, wr1, st1, _ = _run(E, vid, tmp_path, nets, monkeypatch, extra, "redo")
-    assert len(calls) > 2 and not wr0 and not wr1
-    assert len(st0) == 8 and st0 == st1
-    for k in res0:
-        for e_a, e_b in zip(res0[k], res1[k]):
-            assert np.array_equal(e_a, e_b)
+    got = V.run(vid, tmp_path, nets, extra, "redo")
+    assert len(calls) > 2 and not want.written and not got.written
+    assert len(want.streams) == 8 and want.streams == got.streams
+    V.same_ellipses(want.res, got.res)
 
 
 def test_video_frames_that_do_not_fit_take_the_host_path(tmp_path, nets, monkeypatch):
     """Slots of the median stream length: the longer streams are flagged, their frames come down and go through _put_frame_number and
     write -- the very frames the --device_io 1 run writes --, the others still arrive encoded."""
     E, R = _E(), _R()
-    vid = _clip(tmp_path)
+    vid = V.clip(tmp_path)
     base = ["--low_latency", "0", "--device_io", "1"]
-    _, wr0, _, _ = _run(E, vid, tmp_path, nets, monkeypatch, base, "dev")
-    _, _, st1, _ = _run(E, vid, tmp_path, nets, monkeypatch, base + ["--device_jpeg", "1"], "jpg")
+    wr0 = V.run(vid, tmp_path, nets, base, "dev").written
+    st1 = V.run(vid, tmp_path, nets, base + ["--device_jpeg", "1"], "jpg").streams
     sizes = sorted(len(s) for _, s in st1)
     cap = sizes[3]
     real = E.encode_jpeg_device
     monkeypatch.setattr(E, "encode_jpeg_device", lambda frames, quality=90, cap_=None: real(frames, quality, cap))
-    _, wr2, st2, down2 = _run(E, vid, tmp_path, nets, monkeypatch, base + ["--device_jpeg", "1"], "cap")
+    cap_run = V.run(vid, tmp_path, nets, base + ["--device_jpeg", "1"], "cap")
+    wr2, st2, down2 = cap_run.written, cap_run.streams, cap_run.down
     fits = [len(s) <= cap for _, s in st1]
     assert 0 < sum(fits) < 8 and len(wr2) == 8 - sum(fits) and len(st2) == sum(fits)
     assert [s for (_, s), ok in zip(st1, fits) if ok] == [s for _, s in st2]

@@ -2,14 +2,13 @@
 jpeg_decode_refs.py (which test_host_jpeg_decode.py holds against PIL) on the streams of jpeg_decode_cases.py, in both modes and at
 two subsequence lengths; the Python surface; guard bytes; a damaged stream; the video loop with and without the switch."""
 import ctypes
-import io
 
 import numpy as np
 import pytest
 import torch
-from PIL import Image
 
 import jpeg_decode_cases as C
+import video_harness as V
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -166,43 +165,11 @@ def test_bad_arguments(kwargs, word):
 
 
 # ---- the video loop ---------------------------------------------------------------------------------------------------------------------
-def _clip(tmp_path, progressive_at=None):
-    from common import gold
-    E = _E()
-    g = gold("evaluate_real_frames")
-    vid = tmp_path / "clip.avi"
-    w = E.MJPEGWriter(str(vid), 30, (640, 240))
-    for k in range(4):
-        fr = np.concatenate([g["eyes"][2 * (k // 2)], g["eyes"][2 * (k // 2) + 1]], axis=1)
-        if k == progressive_at:
-            buf = io.BytesIO()
-            Image.fromarray(np.stack([fr] * 3, axis=2)).save(buf, format="JPEG", quality=90, progressive=True)
-            assert E.jpeg_parse(buf.getvalue()) is None
-            w.write_jpeg(buf.getvalue())
-        else:
-            w.write(np.stack([fr] * 3, axis=2))
-    w.release()
-    return vid
-
-
-def _run(E, vid, tmp_path, nets, extra, method):
-    """evaluate_ellseg_per_video; returns the three files it wrote: the ellipse dictionary and the two videos' bytes."""
-    bd, net = nets
-    args = E.parse_args(["--path2data", str(tmp_path), "--method", method] + extra)
-    res = E.evaluate_ellseg_per_video(str(vid), args, net, bd, torch.device(DEV))
-    pred = np.load(str(tmp_path / ("clip_pred2_%s.npy" % method)), allow_pickle=True).item()
-    assert set(pred) == set(res) and len(res) == 4 + 8
-    return pred, open(str(tmp_path / ("clip_result_%s.avi" % method)), "rb").read(), open(str(tmp_path / ("clip_edge_%s.avi" % method)), "rb").read()
-
-
-def _same(a, b):
-    assert set(a[0]) == set(b[0])
-    for k in a[0]:
-        for e_a, e_b in zip(a[0][k], b[0][k]):
-            assert e_a.shape == (5,) and np.array_equal(e_a, e_b), (k, e_a, e_b)
-    assert a[1] == b[1], "the result videos differ"
-    assert a[2] == b[2], "the edge videos differ"
-    assert len(a[1]) > 4 * 4096
+def _run(vid, tmp_path, nets, extra, method):
+    """The run's record (video_harness.run); the four-frame clip leaves an ellipse pair per frame and per eye."""
+    r = V.run(vid, tmp_path, nets, extra, method)
+    assert len(r.res) == 4 + 8
+    return r
 
 
 @pytest.mark.parametrize("live", ["0", "1"])
@@ -210,10 +177,10 @@ def test_video_end_to_end_equals_the_host_decode(tmp_path, nets, monkeypatch, li
     """--device_io 1 --device_jpeg 1 --device_decode 1 writes the same three files, byte for byte, as the run without --device_decode
     (after a warm-up run); the decoded frames never exist on the host, and PIL's decoder is not called."""
     E = _E()
-    vid = _clip(tmp_path)
+    vid = V.clip(tmp_path)
     base = ["--low_latency", live, "--device_io", "1", "--device_jpeg", "1"]
-    _run(E, vid, tmp_path, nets, base, "warm")
-    want = _run(E, vid, tmp_path, nets, base, "host")
+    _run(vid, tmp_path, nets, base, "warm")
+    want = _run(vid, tmp_path, nets, base, "host")
     calls, ups = [], []
     real_host, real_up = E._decode_host, E._upload_u8
     monkeypatch.setattr(E, "_decode_host", lambda data: calls.append(1) or real_host(data))
@@ -221,9 +188,9 @@ def test_video_end_to_end_equals_the_host_decode(tmp_path, nets, monkeypatch, li
     monkeypatch.setattr(E, "mjpeg_frames", lambda path: (_ for _ in ()).throw(AssertionError("the host decoder ran")))
     real_dec, sizes = E.decode_jpeg_device, []
     monkeypatch.setattr(E, "decode_jpeg_device", lambda datas, *a, **kw: sizes.append(len(datas)) or real_dec(datas, *a, **kw))
-    got = _run(E, vid, tmp_path, nets, base + ["--device_decode", "1"], "dev")
+    got = _run(vid, tmp_path, nets, base + ["--device_decode", "1"], "dev")
     monkeypatch.undo()
-    _same(want, got)
+    V.same_files(want, got)
     assert not calls and not ups
     assert sizes == ([1] * 4 if live == "1" else [4])           # one decode per frame pair in the live loop, one per batch otherwise
 
@@ -232,10 +199,10 @@ def test_video_end_to_end_equals_the_host_decode(tmp_path, nets, monkeypatch, li
 def test_video_without_device_jpeg(tmp_path, nets, live):
     """--device_io 1 --device_decode 1 alone (PIL encodes the output): the same three files as --device_io 1."""
     E = _E()
-    vid = _clip(tmp_path)
+    vid = V.clip(tmp_path)
     base = ["--low_latency", live, "--device_io", "1"]
-    _run(E, vid, tmp_path, nets, base, "warm")
-    _same(_run(E, vid, tmp_path, nets, base, "host"), _run(E, vid, tmp_path, nets, base + ["--device_decode", "1"], "dev"))
+    _run(vid, tmp_path, nets, base, "warm")
+    V.same_files(_run(vid, tmp_path, nets, base, "host"), _run(vid, tmp_path, nets, base + ["--device_decode", "1"], "dev"))
 
 
 @pytest.mark.parametrize("live", ["0", "1"])
@@ -243,15 +210,15 @@ def test_video_with_a_progressive_frame_and_a_flagged_one(tmp_path, nets, monkey
     """A progressive frame spliced into the video takes the host path; a frame whose flag comes back non-zero (here: forced, and its
     decoded row overwritten) is decoded by PIL at draw time and its batch is done again: the files are still the host decode's."""
     E = _E()
-    vid = _clip(tmp_path, progressive_at=1)
+    vid = V.clip(tmp_path, progressive_at=1)
     base = ["--low_latency", live, "--device_io", "1", "--device_jpeg", "1"]
-    _run(E, vid, tmp_path, nets, base, "warm")
-    want = _run(E, vid, tmp_path, nets, base, "host")
+    _run(vid, tmp_path, nets, base, "warm")
+    want = _run(vid, tmp_path, nets, base, "host")
     calls = []
     real_host = E._decode_host
     monkeypatch.setattr(E, "_decode_host", lambda data: calls.append(1) or real_host(data))
-    got = _run(E, vid, tmp_path, nets, base + ["--device_decode", "1"], "dev")
-    _same(want, got)
+    got = _run(vid, tmp_path, nets, base + ["--device_decode", "1"], "dev")
+    V.same_files(want, got)
     assert len(calls) == 1                                     # the progressive frame, once
     real_dec, flagged = E.decode_jpeg_device, []
 
@@ -264,8 +231,8 @@ def test_video_with_a_progressive_frame_and_a_flagged_one(tmp_path, nets, monkey
         return grey, flags
     monkeypatch.setattr(E, "decode_jpeg_device", spoiled)
     del calls[:]
-    got = _run(E, vid, tmp_path, nets, base + ["--device_decode", "1"], "flag")
-    _same(want, got)
+    got = _run(vid, tmp_path, nets, base + ["--device_decode", "1"], "flag")
+    V.same_files(want, got)
     assert flagged and len(calls) == 2                           # the progressive frame and the flagged one
 
 
@@ -274,24 +241,24 @@ def test_video_redo_after_a_reported_overflow(tmp_path, nets, monkeypatch, live)
     """The re-calibration path with the decode in front: the first overflow query answers "overflowed", the batch is done again from
     the decoded device frames -- same files."""
     E = _E()
-    vid = _clip(tmp_path)
+    vid = V.clip(tmp_path)
     extra = ["--low_latency", live, "--device_io", "1", "--device_jpeg", "1", "--device_decode", "1"]
-    _run(E, vid, tmp_path, nets, extra, "warm")
-    want = _run(E, vid, tmp_path, nets, extra, "dev")
+    _run(vid, tmp_path, nets, extra, "warm")
+    want = _run(vid, tmp_path, nets, extra, "dev")
     real, calls = E._overflowed, []
 
     def once(net):
         calls.append(1)
         return True if len(calls) == 1 else real(net)
     monkeypatch.setattr(E, "_overflowed", once)
-    got = _run(E, vid, tmp_path, nets, extra, "redo")
+    got = _run(vid, tmp_path, nets, extra, "redo")
     assert len(calls) > 2
-    _same(want, got)
+    V.same_files(want, got)
 
 
 def test_video_frame_nobody_decodes_names_the_frame(tmp_path, nets, monkeypatch):
     E = _E()
-    vid = _clip(tmp_path)
+    vid = V.clip(tmp_path)
     real_dec = E.decode_jpeg_device
 
     def flag_all(datas, *a, **kw):
@@ -301,4 +268,4 @@ def test_video_frame_nobody_decodes_names_the_frame(tmp_path, nets, monkeypatch)
     monkeypatch.setattr(E, "decode_jpeg_device", flag_all)
     monkeypatch.setattr(E, "_decode_host", lambda data: None)
     with pytest.raises(SystemExit, match=r"frame 0 .*--device_decode 0"):
-        _run(E, vid, tmp_path, nets, ["--device_io", "1", "--device_decode", "1"], "none")
+        _run(vid, tmp_path, nets, ["--device_io", "1", "--device_decode", "1"], "none")

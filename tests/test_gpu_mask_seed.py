@@ -8,6 +8,7 @@ import pytest
 import torch
 
 import mask_seed_refs as R
+import video_harness as V
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -190,62 +191,42 @@ def test_fit_from_mask_equals_the_oracle_search_on_the_device_seeds():
 
 
 # ---- script level --------------------------------------------------------------------------------------------------------------------
-def _clip(tmp_path):
-    from common import gold
-    from egne_amd import evaluate as E
-    g = gold("evaluate_real_frames")
-    vid = tmp_path / "clip.avi"
-    w = E.MJPEGWriter(str(vid), 30, (640, 240))
-    for k in range(2):
-        fr = np.concatenate([g["eyes"][2 * k], g["eyes"][2 * k + 1]], axis=1)
-        for _ in range(2):
-            w.write(np.stack([fr] * 3, axis=2))
-    w.release()
-    return vid
+def _video(vid, tmp_path, nets, extra, method):
+    """The ellipse dictionary of a run, equal to the one on disk (a class map without a region gives NaN rows: equal_nan)."""
+    r = V.run(vid, tmp_path, nets, extra, method)
+    V.same_ellipses(r.files[0], r.res, equal_nan=True)
+    return r.res
 
 
-def _video(E, vid, tmp_path, nets, extra, method):
-    bd, net = nets
-    args = E.parse_args(["--path2data", str(tmp_path), "--method", method] + extra)
-    res = E.evaluate_ellseg_per_video(str(vid), args, net, bd, torch.device(DEV))
-    on_disk = np.load(str(tmp_path / ("clip_pred2_%s.npy" % method)), allow_pickle=True).item()
-    assert set(on_disk) == set(res) and all(np.array_equal(on_disk[k], res[k], equal_nan=True) for k in res)
-    return res
-
-
-def _equal(res_a, res_b, what):
-    assert set(res_a) == set(res_b)
-    for k in res_a:
-        for e_a, e_b in zip(res_a[k], res_b[k]):
-            assert e_a.shape == (5,) and np.array_equal(e_a, e_b, equal_nan=True), (what, k, e_a, e_b)
+def _equal(res_a, res_b):
+    V.same_ellipses(res_a, res_b, equal_nan=True)
 
 
 def test_video_mask_seed_same_ellipses_through_three_paths(tmp_path, nets):
     """--ellipse_seed mask on the clip of test_evaluate_video_end_to_end: the host path, --device_io 1 and --device_io 1 --low_latency 1
     (seed step inside the captured graph) write the same ellipses.  A first run calibrates the plans."""
-    from egne_amd import evaluate as E
-    vid = _clip(tmp_path)
-    _video(E, vid, tmp_path, nets, ["--ellipse_seed", "mask"], "warm")
-    host = _video(E, vid, tmp_path, nets, ["--ellipse_seed", "mask"], "host")
-    dev = _video(E, vid, tmp_path, nets, ["--ellipse_seed", "mask", "--device_io", "1"], "dev")
-    live = _video(E, vid, tmp_path, nets, ["--ellipse_seed", "mask", "--device_io", "1", "--low_latency", "1"], "live")
+    vid = V.clip(tmp_path)
+    _video(vid, tmp_path, nets, ["--ellipse_seed", "mask"], "warm")
+    host = _video(vid, tmp_path, nets, ["--ellipse_seed", "mask"], "host")
+    dev = _video(vid, tmp_path, nets, ["--ellipse_seed", "mask", "--device_io", "1"], "dev")
+    live = _video(vid, tmp_path, nets, ["--ellipse_seed", "mask", "--device_io", "1", "--low_latency", "1"], "live")
     assert set(k for k in host if isinstance(k, int)) == {0, 1, 2, 3} and all((j, i) in host for j in range(4) for i in range(2))
     for k in host:
         print(k, host[k][0].tolist(), dev[k][0].tolist(), live[k][0].tolist())
-    _equal(host, dev, "host vs device_io")
-    _equal(host, live, "host vs device_io + low_latency")
+    _equal(host, dev)
+    _equal(host, live)
 
 
 def test_video_default_seed_is_pred(tmp_path, nets):
     """The flag left at its default writes what --ellipse_seed pred writes; --ellipse_seed mask writes something else."""
     from egne_amd import evaluate as E
-    vid = _clip(tmp_path)
-    _video(E, vid, tmp_path, nets, [], "warm")
-    a = _video(E, vid, tmp_path, nets, [], "default")
-    b = _video(E, vid, tmp_path, nets, ["--ellipse_seed", "pred"], "pred")
-    _equal(a, b, "default vs pred")
+    vid = V.clip(tmp_path)
+    _video(vid, tmp_path, nets, [], "warm")
+    a = _video(vid, tmp_path, nets, [], "default")
+    b = _video(vid, tmp_path, nets, ["--ellipse_seed", "pred"], "pred")
+    _equal(a, b)
     assert E.parse_args([]).ellipse_seed == "pred"
-    c = _video(E, vid, tmp_path, nets, ["--ellipse_seed", "mask"], "mask")
+    c = _video(vid, tmp_path, nets, ["--ellipse_seed", "mask"], "mask")
     assert any(not np.array_equal(a[k][0], c[k][0], equal_nan=True) for k in a)
 
 

@@ -182,14 +182,9 @@ def test_evaluate_video_end_to_end(tmp_path):
     videos are written and can be read back, the ellipse dictionary holds (iris, pupil) per frame and per eye."""
     from common import bdcn_module, esf_module, gold
     from egne_amd import evaluate as E
+    import video_harness as V
     g = gold("evaluate_real_frames")
-    vid = tmp_path / "clip.avi"
-    w = E.MJPEGWriter(str(vid), 30, (640, 240))
-    for k in range(2):
-        fr = np.concatenate([g["eyes"][2 * k], g["eyes"][2 * k + 1]], axis=1)
-        for _ in range(2):
-            w.write(np.stack([fr] * 3, axis=2))
-    w.release()
+    vid = V.clip(tmp_path)
     dev = torch.device("cuda:0")
     bd, net = bdcn_module().to(dev), esf_module("baseline_edge").to(dev).eval()
     args = E.parse_args(["--path2data", str(tmp_path)])
